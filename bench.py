@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: forward+backward modal-analysis passes/sec on the 100k-tet ord-2 mesh, 64 modes.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     (N > 1 without WORLD_SIZE in the environment: the script re-launches itself as
      python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...,
      one rank per GPU over RCCL, and exits with that job's status; fewer than N visible devices is an error)
@@ -11,6 +11,9 @@ block eigensolve for 64 elastic modes, differentiable frequency read-out, oscill
 backward to (E, nu)) for its own material hypotheses on the shared synthetic mesh, then the scalar
 losses are all-reduced (RCCL) - weak scaling, no other collective.  Rank 0 prints ONE JSON line.
 Inputs are synthetic (Kuhn box mesh) and resident in HBM before the timed region.
+A plain run sets up, warms up, times the K steps and prints the headline; ``--full`` adds the measurements beside it
+(roofline, amortised variant, one hypothesis at a time, API loop, host load, CPU baseline).  ``--dump-outputs DIR`` writes
+what the last timed step's passes returned as .npy files (``dump_outputs``).
 """
 import argparse
 import json
@@ -260,6 +263,16 @@ def parse():
     ap.add_argument("--same-material", action="store_true",
                     help="every step repeats each hypothesis' (E, nu) exactly (rounds 1-5); default: the material moves every step, "
                          "E (1 + 1e-3 s), nu (1 - 5e-4 s), as an optimiser's would - no pass sees the material its lane saw before")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the per-kernel instrumentation of the timed region and the "
+                         "roofline object, the amortised variant, one hypothesis at a time, the kernel statistics, the API loop, the "
+                         "host-load probe and the CPU baseline (each still subject to its own --no-* / --amortised-cycle option). "
+                         "Default: set up, warm up, time the steps, print the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what this rank's passes of the LAST timed step returned to DIR/<name>.npy "
+                         "(hypotheses in order, one row each): loss, grad_E, grad_nu, eigenvalues, freqs (undamped, Hz), audio and "
+                         "eigenvectors_sample (the same rows of every eigenvector, drawn by a fixed seed from the degrees of "
+                         "freedom; vectors of a repeated eigenvalue are fixed only up to a rotation of their subspace)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-baseline-child", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--geom-cpu-child", action="store_true", help=argparse.SUPPRESS)
@@ -1081,6 +1094,39 @@ def cap_torch_threads_at_the_cpu_quota():
             torch.set_num_threads(max(1, cpus))
 
 
+DUMP_VECTOR_ROWS = 4096  # rows of every eigenvector in eigenvectors_sample.npy (fewer when the system is smaller)
+DUMP_SEED = 2024
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """--dump-outputs: the arrays the passes of one step returned (``outs``: ``(PassResult, ModalResult, audio)`` per hypothesis,
+    as ``ModalPipeline.run_steps`` hands them to ``on_step``), stacked over the hypotheses, as float32 / float64 ``path/<name>.npy``.
+    Returns {name: shape}."""
+    def f(x):
+        x = x.detach().cpu()
+        return (x if x.dtype == torch.float64 else x.float()).numpy()
+
+    rs = [r for r, _, _ in outs]
+    n, m = outs[0][1].vectors.shape
+    nrows = min(n, DUMP_VECTOR_ROWS, DUMP_MAX_BYTES // 2 // (4 * m * len(outs)))
+    rows = torch.from_numpy(np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=nrows, replace=False)))
+    arrays = {"loss": np.array([r.loss for r in rs], dtype=np.float64),
+              "grad_E": np.array([r.grad_E for r in rs], dtype=np.float64),
+              "grad_nu": np.array([r.grad_nu for r in rs], dtype=np.float64),
+              "eigenvalues": np.stack([f(r.eigenvalues).reshape(-1) for r in rs]),
+              "freqs": np.stack([f(r.freqs).reshape(-1) for r in rs]),
+              "audio": np.stack([f(audio).reshape(-1) for _, _, audio in outs]),
+              "eigenvectors_sample": np.stack([f(res.vectors[rows.to(res.vectors.device)]) for _, res, _ in outs])}
+    total = sum(x.nbytes for x in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES})")
+    os.makedirs(path, exist_ok=True)
+    for name, x in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), x)
+    return {name: list(x.shape) for name, x in arrays.items()}
+
+
 def main():
     a = parse()
     if not a.cpu_baseline_child and not a.geom_cpu_child:  # (the CPU oracle's children size their own pools)
@@ -1094,6 +1140,8 @@ def main():
     if a.cpu_baseline_child:  # one pass of the CPU oracle, nothing else (no GPU, no torch.distributed)
         print(json.dumps(cpu_baseline_pass(a.cpu_sample_cells, a.order, a.modes, 6 * a.cells ** 3)))
         return
+    if a.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1 (the headline is the time of the timed steps)")
     relaunch_as_ranks(a)  # N > 1: becomes N ranks under torch.distributed.run (never a silent single rank)
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -1195,8 +1243,11 @@ def main():
             cits.append(r.coarse_iterations)
         on_step.total = all_reduce_loss(loss_sum, dev)
         on_step.stamps.append(time.time())
+        if a.dump_outputs:
+            on_step.last = outs  # (ModalPipeline.run_steps keeps every step's results until it returns in any case)
 
     on_step.stamps = []
+    on_step.last = None
 
     steps_done = [0]  # steps run so far (warm-up included): the material of a step depends on its global number
 
@@ -1234,12 +1285,12 @@ def main():
 
     # ---- instrument the dominant kernel: every launch of the fused Chebyshev-term SpMM (fine and corner-node level
     #      alike: they are ONE kernel) on the FIRST hypothesis lane's stream is bracketed by HIP events inside the
-    #      library (ds_profile_stream) - the launches come from the native drivers, not from Python
+    #      library (ds_profile_stream) - the launches come from the native drivers, not from Python (--full only)
     from diffsound_amd import _hip
     lane_ops = [ln.ops for ln in pipe._lanes if ln.ops is not None] or [pipe.ops]
     prof_stream = pipe._lanes[0].stream.cuda_stream if pipe._lanes else torch.cuda.current_stream(dev).cuda_stream
     PROF_CAP = 20000
-    if rank == 0:
+    if rank == 0 and a.full:
         _hip.check(_hip.lib().ds_profile_stream(prof_stream, PROF_CAP), "ds_profile_stream")
     barrier()
     torch.cuda.synchronize()
@@ -1274,17 +1325,21 @@ def main():
                  "idle_fraction": round(max(0.0, 1 - float(g[3]) / dt), 4),
                  "hbm_peak_allocated_gib": round(float(g[4]), 3), "hbm_in_use_on_device_gib": round(float(g[5]), 3)}
                 for r, g in enumerate(gathered)]
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        dumped = {"dir": a.dump_outputs, "hypotheses": [int(h) for h in mine], "arrays": dump_outputs(a.dump_outputs, on_step.last)}
+    on_step.last = None
 
     import ctypes
     pms = (ctypes.c_float * PROF_CAP)()
     pnv, pnz = (ctypes.c_int64 * PROF_CAP)(), (ctypes.c_int64 * PROF_CAP)()
     pnc, pfi = (ctypes.c_int32 * PROF_CAP)(), (ctypes.c_int32 * PROF_CAP)()
-    nrec = int(_hip.lib().ds_profile_collect(pms, pnv, pnz, pnc, pfi, PROF_CAP)) if rank == 0 else 0
+    nrec = int(_hip.lib().ds_profile_collect(pms, pnv, pnz, pnc, pfi, PROF_CAP)) if rank == 0 and a.full else 0
     # ---- the amortised variant: one full pass, then cycle - 1 passes that only read out, render and
     #      differentiate on the kept eigenvectors while the material moves (an optimiser's small steps); reported BESIDE
     #      the headline, never instead of it
     amortised = None
-    if world == 1 and a.amortised_cycle > 1:
+    if world == 1 and a.full and a.amortised_cycle > 1:
         cyc, ncyc = a.amortised_cycle, 2
         torch.cuda.synchronize()
         ta = time.time()
@@ -1308,7 +1363,7 @@ def main():
     #      count, and the literal loop of experiments/material_sync_train.py through the drop-in API - rank 0 of a 1-rank job
     one_hyp = kstats = api = None
     _cg_mark("timed steps + amortised variant")
-    if world == 1 and not a.no_api_path:
+    if world == 1 and a.full and not a.no_api_path:
         one_hyp = one_hypothesis_leg(pipe, hyps, dev, passes=12, steps_done=steps_done[0])
         _cg_mark("one hypothesis at a time")
         kstats = kernel_stats_leg(pipe, hyps, dev)
@@ -1627,12 +1682,14 @@ def main():
             "collective": (f"{a.dist_backend} all-reduce of the scalar loss over {world} ranks" if world > 1 else "none (1 rank)"),
             "process_group": ({"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                                "is_rccl": dist.get_backend() == "nccl"} if world > 1 else None),
-            "host_load": host_load_record(),
+            "host_load": host_load_record() if a.full else None,
             "host_threads": {"hardware_threads": hw_threads, "ranks_on_node": local_world, "lanes_per_rank": min(a.lanes, a.hyp_per_gpu),
                              "lane_threads_on_node": local_world * min(a.lanes, a.hyp_per_gpu), "lapack_threads_per_lane": 1,
                              "within_half_of_hardware_threads": local_world * min(a.lanes, a.hyp_per_gpu) <= hw_threads // 2},
+            "full": a.full,  # (False: the legs beside the headline - roofline, amortised, API path, host load, CPU baseline - did not run)
+            "dumped_outputs": dumped,
         }
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(a.cpu_sample_cells, a.order, a.modes, sysd.T, a.cpu_reps, a.cpu_second_cells)
             out["cpu_baseline"]["memory_safe_restatement"] = memsafe_curve(sysd.T, out["cpu_baseline"].get("cpu_model"))
         print(json.dumps(out))

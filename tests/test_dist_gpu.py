@@ -36,7 +36,7 @@ def ndev():
 
 @pytest.fixture(scope="module")
 def one_rank(ndev):
-    return _bench("--gpus", "1", "--hyp-per-gpu", "4", "--lanes", "2", *SMALL)
+    return _bench("--gpus", "1", "--hyp-per-gpu", "4", "--lanes", "2", "--full", *SMALL)
 
 
 def test_bench_line_contract(one_rank):
@@ -78,6 +78,31 @@ def test_bench_line_contract(one_rank):
     am = d["amortised"]
     assert am["eigen_decompose_cycle"] == 15 and am["unit"] == "passes/s" and am["value"] > d["value"]
     assert len(d["ranks"]) == 1 and d["ranks"][0]["hypotheses_per_step"] == 4 and d["ranks"][0]["fine_iterations"] >= 4
+
+
+def test_plain_line_times_only_the_steps_and_dumps_the_last_one(ndev, one_rank, tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes the last timed step's
+    results, and the same arguments give the same inputs: the step's loss sum equals the --full run's, and a second plain run
+    writes the same arrays."""
+    args = ["--gpus", "1", "--hyp-per-gpu", "4", "--lanes", "2", *SMALL]
+    a = _bench(*args, "--dump-outputs", str(tmp_path / "a"))
+    b = _bench(*args, "--dump-outputs", str(tmp_path / "b"))
+    assert a["full"] is False and one_rank["full"] is True and a["steps"] == 1
+    assert a["roofline"] is None and a["amortised"] is None and a["one_hypothesis"] is None and a["api_path"] is None
+    assert a["host_load"] is None and "cpu_baseline" not in a
+    assert abs(a["value"] - 4 / (a["ms_per_step"] * 1e-3)) < 1e-6 * a["value"]
+    assert a["loss_sum_last_step"] == one_rank["loss_sum_last_step"]
+    names = {"loss", "grad_E", "grad_nu", "eigenvalues", "freqs", "audio", "eigenvectors_sample"}
+    assert set(a["dumped_outputs"]["arrays"]) == names and a["dumped_outputs"]["hypotheses"] == [0, 1, 2, 3]
+    total = 0
+    for name in names:
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype in (np.float32, np.float64) and x.shape[0] == 4 and list(x.shape) == a["dumped_outputs"]["arrays"][name]
+        assert np.isfinite(x).all() and np.array_equal(x, y), name
+        total += x.nbytes
+    assert total <= 64 << 20
+    assert np.load(tmp_path / "a" / "loss.npy").sum() == pytest.approx(a["loss_sum_last_step"], rel=1e-12)
+    assert np.load(tmp_path / "a" / "eigenvalues.npy").shape[1] == 16 and np.load(tmp_path / "a" / "audio.npy").shape[1] == 8000
 
 
 def test_c5_workload_line(ndev):

@@ -286,3 +286,40 @@ def test_rank_cpu_affinity_from_sysfs(tmp_path):
 
     bound, cpus = json.loads(out.stdout.strip().splitlines()[-1])
     assert bound and cpus == list(range(q, 2 * q))
+
+
+def test_bench_dump_outputs_writes_float_arrays_of_the_step(tmp_path):
+    """bench.py --dump-outputs on stand-in results of one step (three hypotheses, host tensors of the shapes a pass returns):
+    one stacked float32 / float64 array per returned quantity, the same eigenvector rows for every hypothesis, and a fixed
+    row draw from one call to the next."""
+    import types
+
+    import bench
+    from diffsound_amd.pipeline import PassResult
+
+    n, m, S = 5000, 6, 80
+    g = torch.Generator().manual_seed(0)
+    outs = []
+    for h in range(3):
+        ev = torch.rand(m, dtype=torch.float64, generator=g) + h
+        r = PassResult(0.5 + h, 1e-9 * h, -2.0 * h, torch.rand(m, 1, generator=g), 7, ev)
+        res = types.SimpleNamespace(vectors=torch.randn(n, m, generator=g))
+        outs.append((r, res, torch.randn(1, S, generator=g)))
+    shapes = bench.dump_outputs(str(tmp_path / "a"), outs)
+    assert bench.dump_outputs(str(tmp_path / "b"), outs) == shapes
+    rows = min(n, bench.DUMP_VECTOR_ROWS)
+    assert shapes == {"loss": [3], "grad_E": [3], "grad_nu": [3], "eigenvalues": [3, m], "freqs": [3, m], "audio": [3, S],
+                      "eigenvectors_sample": [3, rows, m]}
+    load = lambda d, name: np.load(tmp_path / d / f"{name}.npy")
+    assert load("a", "loss").dtype == np.float64 and np.array_equal(load("a", "loss"), [0.5, 1.5, 2.5])
+    assert np.array_equal(load("a", "grad_nu"), [0.0, -2.0, -4.0])
+    assert load("a", "eigenvalues").dtype == np.float64 and np.array_equal(load("a", "eigenvalues")[2], outs[2][0].eigenvalues.numpy())
+    assert load("a", "freqs").dtype == np.float32 and np.array_equal(load("a", "freqs")[1], outs[1][0].freqs.numpy().reshape(-1))
+    assert load("a", "audio").dtype == np.float32 and np.array_equal(load("a", "audio")[0], outs[0][2].numpy().reshape(-1))
+    vs = load("a", "eigenvectors_sample")
+    assert vs.dtype == np.float32 and np.array_equal(vs, load("b", "eigenvectors_sample"))
+    # the sampled rows are distinct rows of each hypothesis' vectors, the same rows for all three
+    row_of = {tuple(outs[0][1].vectors[i].numpy()): i for i in range(n)}
+    picked = [row_of[tuple(v)] for v in vs[0]]
+    assert len(set(picked)) == rows and picked == sorted(picked)
+    assert all(np.array_equal(vs[h], outs[h][1].vectors[picked].numpy()) for h in range(3))

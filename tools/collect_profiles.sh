@@ -1,6 +1,6 @@
 #!/bin/bash
 # Round evidence on the GPU box (run from the repo root): tools/collect_profiles.sh r02
-#   <tag>_bench_n1.json                 bench.py default run (with the CPU baseline)
+#   <tag>_bench_n1.json                 bench.py --full run (roofline, API legs, CPU baseline)
 #   <tag>_bench_kernel_stats.csv        rocprofv3 --kernel-trace --stats of the default run (4 lanes)
 #   <tag>_bench_lanes1_kernel_stats.csv the same with one hypothesis at a time (clean per-kernel durations)
 #   <tag>_spmm_pmc_<kind>.json          FETCH_SIZE / WRITE_SIZE per launch of the SpMM forms (separate passes): fused term fp32 / bf16 / mfma,
@@ -25,7 +25,7 @@ export TMPDIR=/tmp
 out=gpurun_out
 mkdir -p $out
 if [ $part = 1 ] || [ $part = all ]; then
-python3 bench.py > $out/${tag}_bench_n1.json 2> $out/${tag}_bench_stderr.log
+python3 bench.py --full > $out/${tag}_bench_n1.json 2> $out/${tag}_bench_stderr.log
 echo "bench done"; tail -c 300 $out/${tag}_bench_n1.json; echo
 fi
 if [ $part = 1b ] || [ $part = all ]; then
@@ -40,7 +40,7 @@ python3 tools/summarize_prof.py /tmp/prof_l1 $out/${tag}_bench_lanes1_kernel_sta
 # the kernel-alone measurements of the bench line (roofline.avg_launch_ms: hundreds of back-to-back launches after the timed region)
 # under the profiler: a short run whose launches of the fused term, K W and the triad are almost all those
 rm -rf /tmp/prof_solo
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_solo -o bench -- python3 bench.py --no-cpu-baseline --no-api-path --lanes 1 --hyp-per-gpu 1 --steps 1 --warmup 1 --amortised-cycle 1 > $out/${tag}_bench_prof_solo.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_solo -o bench -- python3 bench.py --full --no-cpu-baseline --no-api-path --lanes 1 --hyp-per-gpu 1 --steps 1 --warmup 1 --amortised-cycle 1 > $out/${tag}_bench_prof_solo.log 2>&1
 python3 tools/summarize_prof.py /tmp/prof_solo $out/${tag}_bench_solo_kernel_stats.csv --top 12
 fi
 if [ $part = 2 ] || [ $part = all ]; then
