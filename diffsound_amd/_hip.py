@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 33  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 34  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -85,6 +85,11 @@ _SIGNATURES = {
     "ds_stft_power": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "ds_spec_loss": (_I, [_I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P]),
     "ds_stft_power_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "ds_bem_geometry": (_I, [_P, _I64, _P, _I64, _P, _P]),
+    "ds_bem_assemble_workspace_bytes": (_I64, [_I64]),
+    "ds_bem_assemble": (_I, [_P, _I64, _F, _P, _P, _I64, _P, _I64, _P, _P, _P]),
+    "ds_bem_cgemv": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "ds_bem_potential": (_I, [_P, _I64, _F, _P, _P, _P, _I64, _P, _P]),
 }
 
 class Block64(ctypes.Structure):

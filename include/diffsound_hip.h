@@ -40,7 +40,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 33
+#define DS_ABI_VERSION 34
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -671,6 +671,40 @@ int64_t ds_profile_collect(float* ms, int64_t* nv, int64_t* nnzb, int32_t* ncols
  * (3 n 4 bytes per call) that bench.py quotes the SpMM against.  Not part of the modal path.
  * ---------------------------------------------------------------------------------------------- */
 int ds_stream_triad(float* a, const float* b, const float* c, int64_t n, float s, ds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Helmholtz boundary elements (csrc/bem.hip): exterior Neumann problem in direct form, piecewise-constant
+ * ("DP0") space, one coefficient per triangle.  Replaces the bempp-cl operators of the reference's
+ * src/diffelastic/bem.py (the Python side: diffsound_amd/diffelastic/bem.py).  Complex data is interleaved
+ * fp32 (re, im) pairs, torch.complex64-compatible; matrices are row-major with an explicit leading dimension
+ * in complex elements.  G(x,y) = e^{ikr}/(4 pi r); the quadrature and the near-pair rule: DESIGN.md.
+ *
+ * Face record (DS_BEM_FACE_RECORD floats per face): [0,18) the 6 quadrature points (x, y, z), [18,24) their
+ * weights times the area, [24,27) unit normal (right-hand rule on the vertex order), [27,30) centroid,
+ * [30] diameter (longest edge), [31] area, [32,41) the three vertices, the rest 0.
+ * A pair (i, j) is NEAR when |c_i - c_j| < DS_BEM_NEAR_RATIO * max(h_i, h_j) (every pair that shares a vertex
+ * is near: a centroid lies within 2/3 h of each vertex); a point p is near face j when |p - c_j| <
+ * DS_BEM_NEAR_RATIO * h_j.
+ * ---------------------------------------------------------------------------------------------- */
+#define DS_BEM_FACE_RECORD 48
+#define DS_BEM_NEAR_RATIO 1.75f
+/* Per-face geometry, once per mesh (replaces the bempp grid + DP0 space, bem.py:7-13 and :25): verts (nv x 3)
+ * f32, tris (m x 3) int32 (indices checked by the caller), rec (m x DS_BEM_FACE_RECORD) f32. */
+int ds_bem_geometry(const float* verts, int64_t nv, const int32_t* tris, int64_t m, float* rec, ds_stream_t stream);
+/* Bytes of the workspace ds_bem_assemble needs for n faces (the per-workgroup parts of V g). */
+int64_t ds_bem_assemble_workspace_bytes(int64_t n);
+/* Galerkin assembly (replaces bem.py:36-43 and the V g product of :44): A = -1/2 M + K (n x n complex, lda),
+ * rhs = V g (n complex) from g (n complex), both in one pass; V itself (n x n, ldv) only when V != NULL.
+ * k >= 0.  work: ds_bem_assemble_workspace_bytes(n) bytes.  Bitwise reproducible (no atomics). */
+int ds_bem_assemble(const float* rec, int64_t n, float k, const float* g, float* A, int64_t lda, float* V, int64_t ldv,
+                    float* rhs, void* work, ds_stream_t stream);
+/* y = diag(scale) A x for the complex n x n matrix A (the matvec of the GMRES that replaces bem.py:45-46); scale
+ * (n real) may be NULL (= 1).  lda even, A and x 16-byte aligned.  Fixed reduction order. */
+int ds_bem_cgemv(const float* A, int64_t lda, const float* x, int64_t n, const float* scale, float* y, ds_stream_t stream);
+/* Potential at np points pts (np x 3 f32): out_p = -sum_j g_j int_Tj G(p,y) dy + sum_j u_j int_Tj dG/dn_y(p,y) dy
+ * (replaces bem.py:50-61).  g, u: n complex face coefficients; out: np complex. */
+int ds_bem_potential(const float* rec, int64_t n, float k, const float* g, const float* u, const float* pts, int64_t np,
+                     float* out, ds_stream_t stream);
 
 #ifdef __cplusplus
 }
