@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 34  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 35  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -90,7 +90,18 @@ _SIGNATURES = {
     "ds_bem_assemble": (_I, [_P, _I64, _F, _P, _P, _I64, _P, _I64, _P, _P, _P]),
     "ds_bem_cgemv": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
     "ds_bem_potential": (_I, [_P, _I64, _F, _P, _P, _P, _I64, _P, _P]),
+    "ds_mt_count_workspace_bytes": (_I64, [_I64, _I64, _I64]),
+    "ds_mt_count": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "ds_mt_emit": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ds_mt_backward_workspace_floats": (_I64, [_I64]),
+    "ds_mt_backward": (_I, [_P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P]),
 }
+
+
+class MtCounts(ctypes.Structure):
+    """ds_mt_counts_t of include/diffsound_hip.h."""
+    _fields_ = [("n_used", _I64), ("n_cross", _I64), ("n_side1", _I64), ("n_side3", _I64), ("n_inner", _I64),
+                ("n_face1", _I64), ("n_face2", _I64), ("reserved", _I64)]
 
 class Block64(ctypes.Structure):
     """ds_block64_t of include/diffsound_hip.h."""

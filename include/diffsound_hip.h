@@ -40,7 +40,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 34
+#define DS_ABI_VERSION 35
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -705,6 +705,59 @@ int ds_bem_cgemv(const float* A, int64_t lda, const float* x, int64_t n, const f
  * (replaces bem.py:50-61).  g, u: n complex face coefficients; out: np complex. */
 int ds_bem_potential(const float* rec, int64_t n, float k, const float* g, const float* u, const float* pts, int64_t np,
                      float* out, ds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Differentiable marching tetrahedra (csrc/dmtet.hip): one engine for the reference's three DMTet variants
+ * (src/dmtet/geometry/dmtet_geometry.py:115-272 plain, dmtet_thickness.py:99-200 thickness band,
+ * dmtet_interpolate.py:115-205 interpolated SDF, which is formed by the caller).  Occupancy is 0 < s <= hi with
+ * hi = +inf (thick == NULL) or hi = *thick (DEVICE pointer, one f32: the thickness variant; a crossing edge whose
+ * ends are both > 0 then has t subtracted from both values).  Outputs equal the reference's bit for bit.
+ *
+ * Per-grid tables (DEVICE int32, built once per grid by the caller): tets (T x 4); the distinct edges ea[e] < eb[e]
+ * sorted by (a, b) (ds_edge_table); tet_edge (T x 6) = the edge id of local edges [01,02,03,12,13,23]; the vertex
+ * -> incident-edge CSR vptr (n + 1) / vadj (2 E).  Indices are the caller's to check (ds_edge_table does).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct {
+    int64_t n_used;  /* kept grid vertices (occupied and in some tet): output vertices [0, n_used) */
+    int64_t n_cross; /* crossing edges: output vertices [n_used, n_used + n_cross) */
+    int64_t n_side1; /* output tets of the 1-tet classes (1, 2, 4, 8) */
+    int64_t n_side3; /* output tets of the 3-tet classes (3 per source tet) */
+    int64_t n_inner; /* output tets of class 15 */
+    int64_t n_face1; /* surface faces of the 1-triangle classes */
+    int64_t n_face2; /* surface faces of the 2-triangle classes (2 per source tet) */
+    int64_t reserved;
+} ds_mt_counts_t;
+/* Bytes of the workspace ds_mt_count needs (-1 if the sizes are out of range). */
+int64_t ds_mt_count_workspace_bytes(int64_t n, int64_t T, int64_t E);
+/* Replaces the occupancy / valid-tet / torch.unique(dim=0) / mask.sum() part of DMTet.__call__ (dmtet_geometry.py:
+ * 122-154, dmtet_thickness.py:107-131, dmtet_interpolate.py:124-145).  sdf (n) f32.  Writes toff (T x 5 int32: each
+ * tet's first row in the 1-tet, 3-tet, inner, 1-face and 2-face sections), edge_id (E: number of each crossing edge
+ * among the crossing edges) and vert_id (n: number of each kept vertex), then copies ONE ds_mt_counts_t to the HOST
+ * `counts` and synchronises `stream` - the only synchronisation of a forward. */
+int ds_mt_count(const float* sdf, int64_t n, const int32_t* tets, int64_t T, const int32_t* ea, const int32_t* eb,
+                int64_t E, const int32_t* vptr, const float* thick, int32_t* toff, int32_t* edge_id, int32_t* vert_id,
+                void* work, int64_t work_bytes, ds_mt_counts_t* counts, ds_stream_t stream);
+/* Replaces the interpolation, the gathers of the split tets and faces, the inner tets and the final torch.unique
+ * compaction (dmtet_geometry.py:155-272, dmtet_thickness.py:133-200, dmtet_interpolate.py:146-205).  pos (n x 3) f32;
+ * counts = the record ds_mt_count returned (HOST).  verts ((n_used + n_cross) x 3) f32: kept grid vertices ascending,
+ * then the edge vertices p_a (-s_b)/(s_a - s_b) + p_b s_a/(s_a - s_b) in fp32 without contraction; out_tets
+ * ((n_side1 + n_side3 + n_inner) x 4) int64; out_faces ((n_face1 + n_face2) x 3) int64 indices of edge vertices
+ * (may be NULL); vsrc (n_used) the grid vertex of each kept vertex; xedge (n_cross) the edge of each edge vertex. */
+int ds_mt_emit(const float* pos, const float* sdf, int64_t n, const int32_t* tets, int64_t T, const int32_t* tet_edge,
+               const int32_t* ea, const int32_t* eb, int64_t E, const int32_t* vptr, const float* thick,
+               const int32_t* toff, const int32_t* edge_id, const int32_t* vert_id, const ds_mt_counts_t* counts,
+               float* verts, int64_t* out_tets, int64_t* out_faces, int32_t* vsrc, int32_t* xedge, ds_stream_t stream);
+/* Floats of the workspace ds_mt_backward needs for dL/dt. */
+int64_t ds_mt_backward_workspace_floats(int64_t n_cross);
+/* Autograd of the above (the reference relies on torch autograd through dmtet_geometry.py:155-173 and the final
+ * gather all_verts[all_unique_tets]): grad_verts ((n_used + n_cross) x 3) -> dpos (n x 3), dsdf (n) by a gather
+ * over the CSR (kept vertices pass their gradient through; edge vertices add the closed-form derivatives), and,
+ * when dt != NULL, dL/dt (one f32) by fixed-order partial sums in work (ds_mt_backward_workspace_floats).  No
+ * atomics: bitwise reproducible. */
+int ds_mt_backward(const float* grad_verts, const float* pos, const float* sdf, int64_t n, const int32_t* ea,
+                   const int32_t* eb, int64_t E, const int32_t* vptr, const int32_t* vadj, const float* thick,
+                   const int32_t* edge_id, const int32_t* vert_id, const int32_t* xedge, int64_t n_used,
+                   int64_t n_cross, float* dpos, float* dsdf, float* dt, float* work, ds_stream_t stream);
 
 #ifdef __cplusplus
 }
