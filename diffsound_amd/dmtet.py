@@ -12,6 +12,9 @@ Here one engine (csrc/dmtet.hip) serves all three variants and returns the refer
 
 ``DMTet``, ``DMTetThickness`` and ``DMTetInterpolate`` take the reference classes' call signatures;
 ``DMTetGeometry`` is the reference's shape-fitting module (an MLP SDF on a deformable tet grid).
+``DMTetThicknessGeometry`` and ``DMTetInterpolateGeometry`` are the ``DMTetGeometry`` classes of the reference's
+dmtet_thickness.py and dmtet_interpolate.py: a fixed SDF on the grid, taken from a mesh file by
+``diffsound_amd.meshsdf`` (the reference: open3d), with one learnable coefficient.
 """
 import ctypes
 
@@ -19,11 +22,11 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _hip, meshgen
+from . import _hip, meshgen, meshsdf
 from .diffelastic.mesh import largest_connected_component
 
 __all__ = ["marching_tets", "grid_tables", "kuhn_grid", "WeightedParam", "DMTet", "DMTetThickness", "DMTetInterpolate",
-           "DMTetGeometry", "sdf_reg_loss", "PositionalEncoding", "NerfWithPositionEncoding",
+           "DMTetGeometry", "DMTetThicknessGeometry", "DMTetInterpolateGeometry", "TriangleMesh", "sdf_reg_loss", "PositionalEncoding", "NerfWithPositionEncoding",
            "largest_connected_component"]
 
 # ds_edge_table's local edge order is (01)(12)(02)(03)(13)(23); DMTet's is [01, 02, 03, 12, 13, 23]
@@ -355,3 +358,178 @@ class DMTetGeometry(torch.nn.Module):
 
     def reg_loss(self):
         return sdf_reg_loss(self.sdf, self.all_edges).mean() * self.sdf_regularizer
+
+
+class TriangleMesh:
+    """What ``getMesh(return_triangle=True)`` returns: the two fields of the reference's render.mesh.Mesh that the
+    generate scripts' .obj export reads."""
+
+    def __init__(self, v_pos, t_pos_idx):
+        self.v_pos = v_pos
+        self.t_pos_idx = t_pos_idx
+
+
+def _summary_writer(FLAGS):
+    """The reference's ``SummaryWriter(FLAGS.out_dir + "/tensorboard")`` unless FLAGS has ``without_tensorboard``.
+    The one deviation: where the tensorboard package does not import, None (nothing is logged) instead of an
+    ImportError at module import."""
+    if hasattr(FLAGS, "without_tensorboard"):
+        return None
+    try:
+        from torch.utils.tensorboard import SummaryWriter
+    except ImportError:
+        return None
+    return SummaryWriter(FLAGS.out_dir + "/tensorboard")
+
+
+class _MeshSdfGeometry(torch.nn.Module):
+    """What the two classes below share (dmtet_thickness.py:204-248 and :298-326, dmtet_interpolate.py:209-262 and
+    :303-360 are the same lines): the grid, its edges, the SDF of a mesh file at the grid vertices (positive inside)
+    and the way from a marched tet mesh to a DiffSoundObj."""
+
+    def __init__(self, grid_res, scale, FLAGS, grid=None):
+        super().__init__()
+        dev = _default_device()
+        self.scale = scale
+        self.FLAGS = FLAGS
+        self.grid_res = grid_res
+        writer = _summary_writer(FLAGS)
+        if writer is not None:
+            self.writer = writer
+        if grid is None:
+            tets = np.load("data/tets/{}_tets.npz".format(self.grid_res))
+            vertices, indices = tets["vertices"], tets["indices"]
+        else:
+            vertices, indices = grid
+        self.base_verts = torch.as_tensor(np.asarray(vertices), dtype=torch.float32).to(dev)
+        self.verts = self.base_verts * self.scale
+        self.indices = torch.as_tensor(np.asarray(indices), dtype=torch.long).to(dev)
+        self.generate_edges()
+        self.sdf = torch.zeros_like(self.verts[:, 0])
+
+    def generate_edges(self):
+        """all_edges: the distinct grid edges (a < b), sorted (the reference's torch.unique of the sorted pairs)."""
+        with torch.no_grad():
+            ea, eb, _ = _hip.edge_table(self.indices, self.verts.shape[0])
+            self.all_edges = torch.stack([ea, eb], dim=1)
+
+    @torch.no_grad()
+    def getAABB(self):
+        return torch.min(self.verts, dim=0).values, torch.max(self.verts, dim=0).values
+
+    def get_largest_connected_component(self, verts, tets):
+        return largest_connected_component(verts, tets)
+
+    def _mesh_sdf(self, mesh_dir):
+        """The SDF of the .obj file at the grid vertices, positive inside: the reference negates open3d's signed
+        distance (dmtet_thickness.py:309-311)."""
+        vertices, faces = meshsdf.read_obj(mesh_dir)
+        signed_distance = meshsdf.MeshDistance(vertices, faces, device=self.verts.device).signed_distance(self.verts)
+        return -signed_distance.reshape(-1)
+
+    def _finish_mesh(self, marched, return_triangle):
+        verts, faces, verts_tetmesh, tets_tetmesh = marched
+        if return_triangle:
+            return TriangleMesh(verts, faces)
+        from .diffelastic.diff_model import DiffSoundObj
+        from .diffelastic.material_model import MatSet
+
+        verts_tetmesh, tets_tetmesh = self.get_largest_connected_component(verts_tetmesh, tets_tetmesh)
+        mat = getattr(MatSet, self.FLAGS.mat) if hasattr(self.FLAGS, "mat") else MatSet.Ceramic
+        return DiffSoundObj(verts_tetmesh, tets_tetmesh, mode_num=self.FLAGS.mode_num, order=self.FLAGS.order, mat=mat)
+
+    def _audio_loss(self, target, it, name, coef):
+        """tick's body: eigenvalue loss of the current mesh, printed and logged under ``name``."""
+        sound_obj = self.getMesh()
+        sound_obj.eigen_decomposition()
+        vals = sound_obj.get_vals()
+        audio_loss = ((vals - target) ** 2 / target ** 2).mean()
+        print(name, coef().item(), "audio_loss", audio_loss.item())
+        writer = getattr(self, "writer", None)
+        if writer is not None:
+            writer.add_scalar("loss", audio_loss.item(), it)
+            writer.add_scalar(name, coef().item(), it)
+        return audio_loss
+
+
+class DMTetThicknessGeometry(_MeshSdfGeometry):
+    """The reference's dmtet_thickness.DMTetGeometry (:203-326): the shell ``0 < sdf <= thickness_coef *
+    max_thickness`` of a mesh file's SDF; the one parameter set is the thickness coefficient's.  Constructor
+    ``(grid_res, scale, FLAGS)`` plus ``grid=(vertices, indices)`` in place of data/tets/{grid_res}_tets.npz."""
+
+    def __init__(self, grid_res, scale, FLAGS, grid=None):
+        super().__init__(grid_res, scale, FLAGS, grid=grid)
+        self.marching_tets = DMTetThickness()
+
+    def getMesh(self, return_triangle=False, thickness_coef=None):
+        return self._finish_mesh(self.marching_tets(self.verts, self.sdf, self.indices, thickness_coef), return_triangle)
+
+    def tick(self, target, it, FLAGS):
+        return self._audio_loss(target, it, "thickness", self.marching_tets.thickness_coef)
+
+    def apply_sdf(self, init_mesh_dir):
+        self.sdf = self._mesh_sdf(init_mesh_dir)
+        self.marching_tets.max_thickness = self.sdf.max()
+
+    def parameters(self):
+        return self.marching_tets.thickness_coef.parameters()
+
+    def get_eigenvalues(self, thickness_coef=None):
+        with torch.no_grad():
+            sound_obj = self.getMesh(thickness_coef=thickness_coef)
+            sound_obj.eigen_decomposition()
+            vals = sound_obj.get_vals()
+        return vals
+
+    def get_thickness(self):
+        return self.marching_tets.thickness_coef()
+
+
+class DMTetInterpolateGeometry(_MeshSdfGeometry):
+    """The reference's dmtet_interpolate.DMTetGeometry (:208-374): the blend ``c * sdf1 + (1 - c) * sdf2`` of two mesh
+    files' SDFs (``apply_sdf2``), or one SDF alone (``apply_sdf`` with ``using_interp=False``); the one parameter set
+    is the interpolation coefficient's.  Constructor as DMTetThicknessGeometry."""
+
+    def __init__(self, grid_res, scale, FLAGS, grid=None):
+        super().__init__(grid_res, scale, FLAGS, grid=grid)
+        self.marching_tets = DMTetInterpolate()
+
+    def getMesh(self, return_triangle=False, interp_coef=None, using_interp=True):
+        if using_interp:
+            marched = self.marching_tets(self.verts, self.sdf1, self.sdf2, self.indices, interp_coef)
+        else:
+            marched = self.marching_tets(self.verts, self.sdf, None, self.indices, interp_coef)
+        return self._finish_mesh(marched, return_triangle)
+
+    def tick(self, target, it, FLAGS):
+        return self._audio_loss(target, it, "interp_coef", self.marching_tets.interp_coef)
+
+    def apply_sdf(self, mesh_dir):
+        self.sdf = self._mesh_sdf(mesh_dir)
+
+    def apply_sdf2(self, mesh_dir1, mesh_dir2):
+        self.sdf1 = self._mesh_sdf(mesh_dir1)
+        self.sdf2 = self._mesh_sdf(mesh_dir2)
+
+    def parameters(self):
+        return self.marching_tets.interp_coef.parameters()
+
+    def get_eigenvalues(self, interp_coef=None, using_interp=True):
+        with torch.no_grad():
+            sound_obj = self.getMesh(interp_coef=interp_coef, using_interp=using_interp)
+            sound_obj.eigen_decomposition()
+            vals = sound_obj.get_vals()
+        return vals
+
+    def get_thickness(self):
+        return self.marching_tets.interp_coef()
+
+    def init_coef(self, target):
+        optimizer = torch.optim.Adam(self.marching_tets.interp_coef.parameters(), lr=1e-1)
+        for _ in range(3000):
+            coef = self.marching_tets.interp_coef()
+            loss = (coef - target) ** 2
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+        print(f"coef init to {self.marching_tets.interp_coef().item()}")

@@ -40,7 +40,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 35
+#define DS_ABI_VERSION 36
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -758,6 +758,36 @@ int ds_mt_backward(const float* grad_verts, const float* pos, const float* sdf, 
                    const int32_t* eb, int64_t E, const int32_t* vptr, const int32_t* vadj, const float* thick,
                    const int32_t* edge_id, const int32_t* vert_id, const int32_t* xedge, int64_t n_used,
                    int64_t n_cross, float* dpos, float* dsdf, float* dt, float* work, ds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Signed distance from a triangle mesh to points (csrc/meshsdf.hip, ABI 36).  Replaces open3d's
+ * RaycastingScene.compute_signed_distance of the reference's shape loops (src/dmtet/geometry/dmtet_thickness.py:
+ * 301-314, dmtet_interpolate.py:318-351, experiments/geometry_train.py:170-197).  Brute force over all (point, face)
+ * pairs in fp32; per point the exact point-triangle distance to the nearest face, that face (the lowest index on
+ * equal squared distances), and the generalised winding number (sum of the signed solid angles / 4 pi).  Signed
+ * distance: negative inside, inside = winding number > 0.5, so faces must be wound counter-clockwise seen from
+ * outside.  No atomics; a point's result does not depend on the other points of the call.
+ *
+ * Face record (DS_MESH_SDF_FACE_RECORD floats per face, 16-byte aligned): [0,9) the vertices a, b, c;
+ * [9,12) 1/|b-a|^2, 1/|c-b|^2, 1/|a-c|^2 (0 for a zero-length edge); [12,15) the unit normal (b-a) x (c-a);
+ * [15] 1 when the face has area, else 0 (such a face gives the distance to its segment or point and no solid angle).
+ * ---------------------------------------------------------------------------------------------- */
+#define DS_MESH_SDF_FACE_RECORD 16
+/* Once per mesh: verts (V x 3) f32, faces (F x 3) int32 (indices checked by the caller) -> face_records
+ * (F x DS_MESH_SDF_FACE_RECORD) f32. */
+int ds_mesh_sdf_pack(const float* verts, const int32_t* faces, int64_t V, int64_t F, float* face_records,
+                     ds_stream_t stream);
+/* Bytes of the workspace for the launch shape that splits the faces across workgroups: what ds_mesh_sdf_query
+ * should be given for P points and F faces.  0 when the one-launch shape is the better one (many points, or one
+ * chunk of faces) and force_split == 0; -1 when the sizes are out of range. */
+int64_t ds_mesh_sdf_workspace_bytes(int64_t P, int64_t F, int force_split);
+/* Per query: points (P x 3) f32 -> out_signed (P) f32 and, where not NULL, out_unsigned (P) f32, out_face (P) int32,
+ * out_winding (P) f32.  work == NULL: one launch.  work != NULL (work_bytes >= ds_mesh_sdf_workspace_bytes(P, F, 1)):
+ * the faces are split across workgroups and a second kernel combines the parts in fixed order; both shapes give the
+ * same bits.  A non-finite coordinate gives a non-finite result (the Python side rejects such input). */
+int ds_mesh_sdf_query(const float* points, int64_t P, const float* face_records, int64_t F, float* out_signed,
+                      float* out_unsigned, int32_t* out_face, float* out_winding, void* work, int64_t work_bytes,
+                      ds_stream_t stream);
 
 #ifdef __cplusplus
 }

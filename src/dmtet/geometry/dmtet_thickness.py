@@ -1,0 +1,6 @@
+"""src.dmtet.geometry.dmtet_thickness: this project's classes under the reference's module and class names
+(``DMTet`` = diffsound_amd.dmtet.DMTetThickness, ``DMTetGeometry`` = diffsound_amd.dmtet.DMTetThicknessGeometry).  The SDF of a mesh file comes
+from diffsound_amd.meshsdf; nothing here imports open3d, the render stack or, at import time, TensorBoard."""
+from diffsound_amd.dmtet import DMTetThickness as DMTet  # noqa: F401
+from diffsound_amd.dmtet import DMTetThicknessGeometry as DMTetGeometry  # noqa: F401
+from diffsound_amd.dmtet import WeightedParam  # noqa: F401
