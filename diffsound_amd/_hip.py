@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 36  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 37  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -98,6 +98,11 @@ _SIGNATURES = {
     "ds_mesh_sdf_pack": (_I, [_P, _P, _I64, _I64, _P, _P]),
     "ds_mesh_sdf_workspace_bytes": (_I64, [_I64, _I64, _I]),
     "ds_mesh_sdf_query": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    "ds_sinkhorn_workspace_floats": (_I64, [_I64, _I64, _I64]),
+    "ds_sinkhorn_bbox": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "ds_sinkhorn_loop": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _I, _I, _P, _P]),
+    "ds_sinkhorn_final": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P]),
+    "ds_sinkhorn_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P, _P, _P]),
 }
 
 

@@ -40,7 +40,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 36
+#define DS_ABI_VERSION 37
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -788,6 +788,41 @@ int64_t ds_mesh_sdf_workspace_bytes(int64_t P, int64_t F, int force_split);
 int ds_mesh_sdf_query(const float* points, int64_t P, const float* face_records, int64_t F, float* out_signed,
                       float* out_unsigned, int32_t* out_face, float* out_winding, void* work, int64_t work_bytes,
                       ds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Debiased Sinkhorn divergence between point clouds (csrc/sinkhorn.hip, ABI 37).  Replaces geomloss==0.2.6
+ * SamplesLoss("sinkhorn", p=2, blur, scaling, debias, reach=None) on its tensorized backend, which the reference's
+ * spectral loss calls (src/ddsp/mss_loss.py:104-117).  Cost C(x, y) = |x - y|^2 / 2 from the coordinates on the fly;
+ * softmin_eps(C, h)_i = -eps LSE_j(h_j - C_ij / eps).  Memory O(B (N + M) D): no N x M matrix.  No atomics; a
+ * batch's result does not depend on B or on its index, and two runs give the same bits.
+ *
+ * x (B x N x D) f32, y (B x M x D) f32, a (B x N) f32, b (B x M) f32 weights (> 0; the caller passes 1/N, 1/M for
+ * uniform ones), 1 <= D <= 32.  The caller fetches the bbox record, checks it and derives the eps schedule (the one
+ * synchronisation of a call); nothing else here synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+/* Floats of the workspace of one call: log a, log b, two potential slots and the last step's LSEs (B (N + M) +
+ * 3 B (2N + 2M)); -1 when the sizes are out of range.  The backward reads what ds_sinkhorn_final left there. */
+int64_t ds_sinkhorn_workspace_floats(int64_t B, int64_t N, int64_t M);
+/* out (3 D + 3) f32: [0, D) per-coordinate minimum over every point of x and y of every batch, [D, 2D) maximum,
+ * [2D] least a, [2D + 1] least b, [2D + 2, 3D + 3) counts of non-finite values (one per coordinate, then the
+ * weights).  The diameter is the norm of max - min. */
+int ds_sinkhorn_bbox(const float* x, const float* y, const float* a, const float* b, int64_t B, int64_t N, int64_t M,
+                     int64_t D, float* out, ds_stream_t stream);
+/* The whole eps loop: f_ba, g_ab (and with debias f_aa, g_bb) initialised at eps_list[0] (HOST array of n_eps
+ * positive values), then for every eps of the list the four softmins and the averaging (f + ft) / 2, one launch per
+ * eps.  The potentials end in the workspace. */
+int ds_sinkhorn_loop(const float* x, const float* y, const float* a, const float* b, int64_t B, int64_t N, int64_t M,
+                     int64_t D, const float* eps_list, int n_eps, int debias, float* work, ds_stream_t stream);
+/* The last extrapolation at eps (= blur^2) without averaging, keeping each row's LSE, then per batch
+ * loss[b] = <a, f_ba - f_aa> + <b, g_ab - g_bb> (debias) or <a, f_ba> + <b, g_ab>, summed in fp64. */
+int ds_sinkhorn_final(const float* x, const float* y, const float* a, const float* b, int64_t B, int64_t N, int64_t M,
+                      int64_t D, float eps, int debias, float* work, double* loss, ds_stream_t stream);
+/* dS/dx_i = g_b a_i (sum_j P_ij (x_i - y_j) - sum_k Q_ik (x_i - x_k)) with P, Q the row-softmax weights of the last
+ * f_ba, f_aa softmins (what autograd gives through geomloss's last step), and the mirror image for y; grad_loss (B)
+ * f32 on the device.  grad_x / grad_y may be NULL. */
+int ds_sinkhorn_backward(const float* x, const float* y, const float* a, const float* b, int64_t B, int64_t N,
+                         int64_t M, int64_t D, float eps, int debias, const float* work, const float* grad_loss,
+                         float* grad_x, float* grad_y, ds_stream_t stream);
 
 #ifdef __cplusplus
 }
