@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 37  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 38  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -103,6 +103,9 @@ _SIGNATURES = {
     "ds_sinkhorn_loop": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _I, _I, _P, _P]),
     "ds_sinkhorn_final": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P]),
     "ds_sinkhorn_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P, _P, _P]),
+    "ds_deform_tables": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _P, _P, _P]),
+    "ds_deform_gradient": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _I64, _I, _P, _P]),
+    "ds_deform_force": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P]),
 }
 
 

@@ -12,6 +12,21 @@ behaviour (gradients reach ``material_model.{youngs,poisson}.probablity``), so
   get_undamped_freqs (:371-388)  ->  lambda_i + lam(theta) a_i + mu(theta) b_i - lambda_i m_i with the
        quadratic forms a_i = u^T K_lambda u, b_i = u^T K_mu u, m_i = u^T M u computed once per
        eigendecomposition (fp64) instead of a matrix-free (modes x Gauss points) sweep per epoch.
+
+Custom material models.  ``mat_model`` may be any module with ``forward(F)`` and ``jacobian_F()`` like the reference's
+(:314-328, :371-388).  A model WITHOUT a ``lame`` attribute is a custom model; the models above keep the path just
+described.  For a custom model
+
+  stiff_func          is the reference's chain ``deform.gradient_batch -> material_model(F) -> deform.stress_to_force_batch``
+       on csrc/deform.hip: autograd reaches the model's parameters through torch and ``x`` through the kernels; the model
+       is called with F of shape (batch, T*G, 3, 3) float32.  F and the stress take batch * T * G * 36 bytes each
+       (G = (order+2)^3 Gauss points per element) and autograd keeps them, as in the reference; there is no chunking.
+  update_stiff_matrix reads the tangent C = jacobian_F() at F = 0 (9x9, like :190) and needs it isotropic,
+       C_ijkl = mu (d_ik d_jl + d_il d_jk) + lam d_ij d_kl (``isotropic_lame``); (lam, mu) then go through the same
+       assembly and eigensolver as above.  Any other tangent raises NotImplementedError: the eigendecomposition with an
+       anisotropic tangent is not built (``stiff_func`` works, and ``lobpcg_func(obj.stiff_func, obj.mass_matrix, ...)``
+       takes a callable).
+  get_undamped_freqs  is the reference's formula, lambda + diag(U^T stiff_func(U)) - lambda m, with U = U_hat.float().
 """
 import numpy as np
 import torch
@@ -98,6 +113,32 @@ class TrainableLinear(nn.Module):
         return J.reshape(1, 3, 3, 1, 3, 3)
 
 
+_ANISOTROPIC = ("diffsound_amd: the material model's tangent jacobian_F() is not isotropic ({why}); the "
+                "eigendecomposition with an anisotropic tangent is not built.  stiff_func works for this model, and "
+                "lobpcg_func(obj.stiff_func, obj.mass_matrix, ...) takes a callable.")
+
+
+def isotropic_lame(C, rtol=1e-5):
+    """(lam, mu) of a 9x9 tangent d vec(P) / d vec(F) (row 3i+j, column 3k+l) of the isotropic form
+    C_ijkl = mu (d_ik d_jl + d_il d_jk) + lam d_ij d_kl: lam = the mean of C_iijj, mu = the mean of C_ijij over
+    i != j.  Raises NotImplementedError when C differs from that form by more than rtol * max|C| anywhere - a test of
+    form, not a measurement: the margin is for a model whose parameters are fp32.  Pure host arithmetic in fp64."""
+    C = np.asarray(C.detach().cpu() if isinstance(C, torch.Tensor) else C, dtype=np.float64)
+    if C.size != 81 or not np.isfinite(C).all():
+        raise NotImplementedError(_ANISOTROPIC.format(why=f"81 finite entries expected, got shape {C.shape}"))
+    C4 = C.reshape(3, 3, 3, 3)
+    off = [(i, j) for i in range(3) for j in range(3) if i != j]
+    lam = float(np.mean([C4[i, i, j, j] for i, j in off]))
+    mu = float(np.mean([C4[i, j, i, j] for i, j in off]))
+    d = np.eye(3)
+    iso = mu * (np.einsum("ik,jl->ijkl", d, d) + np.einsum("il,jk->ijkl", d, d)) + lam * np.einsum("ij,kl->ijkl", d, d)
+    scale = float(np.abs(C4).max())
+    resid = float(np.abs(C4 - iso).max())
+    if scale == 0.0 or resid > rtol * scale:
+        raise NotImplementedError(_ANISOTROPIC.format(why=f"residual {resid:.3e} against max|C| = {scale:.3e}"))
+    return lam, mu
+
+
 def build_model(mesh_dir, mode_num, order, mat, task, vertices=None, tets=None, scale_range=None, init_scale=None):
     """reference :98-113."""
     if task == "material" or task == "mat_baseline":
@@ -154,6 +195,7 @@ class DiffSoundObj:
         self._warm = None
         self._sparse_cache = {}
         self.last_result = None
+        self._deform = None
 
     # ------------------------------------------------------------------ parameters
     def parameters(self):
@@ -182,7 +224,22 @@ class DiffSoundObj:
                                      self.material_model.mat.density)
         return self._system
 
+    @property
+    def deform(self):
+        """The Deform operators of the current ``tetmesh`` (reference :135), built on first use."""
+        if self._deform is None or self._deform.tetmesh is not self.tetmesh:
+            from .deform import Deform
+
+            self._deform = Deform(self.tetmesh)
+        return self._deform
+
+    @property
+    def _custom_material(self):
+        return not hasattr(self.material_model, "lame")
+
     def _current_lame(self):
+        if self._custom_material:  # the tangent at F = 0, as the reference's assembly reads it (:190)
+            return isotropic_lame(self.material_model.jacobian_F().reshape(9, 9).double())
         lam, mu = self.material_model.lame()
         return float(lam), float(mu)
 
@@ -256,7 +313,10 @@ class DiffSoundObj:
     def get_undamped_freqs(self):
         """(mode_num, 1) float32; gradient -> material parameters (reference :371-388)."""
         pred = self.eigenvalues
-        if self.task != "gt":
+        if self.task != "gt" and self._custom_material:  # the reference's matrix-free bracket (:381-387)
+            U = self.U_hat.float()
+            pred = pred + (U * self.stiff_func(U)).sum(0) - pred * self._m
+        elif self.task != "gt":
             lam, mu = self.material_model.lame()  # autograd leaves live on the host like the reference's
             dev = pred.device
             pred = pred + (lam.to(dev) * self._a + mu.to(dev) * self._b) - pred * self._m
@@ -273,6 +333,10 @@ class DiffSoundObj:
     def stiff_func(self, x_in):
         """K(theta) x with autograd to the material parameters (reference :314-328, matrix-free there)."""
         x = x_in.unsqueeze(1) if x_in.dim() == 1 else x_in
+        if self._custom_material:  # the reference's chain; F and the stress are x.shape[1] * T * G * 36 bytes each
+            F = self.deform.gradient_batch(x.transpose(0, 1).reshape(x.shape[1], -1, 3))
+            force = self.deform.stress_to_force_batch(self.material_model(F)).transpose(0, 1)
+            return force.squeeze(1) if x_in.dim() == 1 else force
         ops = self._ops
         xf = self.system.rows_to_internal(x.detach().float()).contiguous()
         pad = (-xf.shape[1]) % 4

@@ -40,7 +40,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 37
+#define DS_ABI_VERSION 38
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -823,6 +823,35 @@ int ds_sinkhorn_final(const float* x, const float* y, const float* a, const floa
 int ds_sinkhorn_backward(const float* x, const float* y, const float* a, const float* b, int64_t B, int64_t N,
                          int64_t M, int64_t D, float eps, int debias, const float* work, const float* grad_loss,
                          float* grad_x, float* grad_y, ds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Deformation gradient at the Gauss points and the stress -> nodal force gather (csrc/deform.hip, ABI 38).  Replaces
+ * the reference's Deform (src/diffelastic/deform.py:8-180) without its materialised tables: the physical shape
+ * gradients B[t,g] = D[g] inv(A_t) are recomputed per element from the four corner coordinates (A_t = the columns
+ * v1-v4, v2-v4, v3-v4, src/diffelastic/mesh.py:58-99; adjugate over determinant in fp32).  No atomics; a column's
+ * result does not depend on the other columns of the call, and two runs give the same bits.
+ *
+ * Common arguments: verts (nv x 3) f32; tets (T x N) int32, N = 4 (order 1) or 10 (order 2), indices checked by the
+ * caller; dtab (G x N x 3) f32 = dN/dL at the Gauss points times dL/dx, gw (G) f32 the Gauss weights, G =
+ * (order + 2)^3 (deform.py:12-17, 47-56).  Gauss-point tensors are indexed t * G + g like the reference's.
+ * ---------------------------------------------------------------------------------------------- */
+/* Any of: sfd (T*G x N x 3) f32 = B (deform.py:35-68), intw (T*G) f32 = gw[g] |det A_t| (deform.py:136-147), det (T)
+ * f32 = det A_t (the caller's degenerate-element check).  NULL outputs are skipped.  For API parity and tests: the two
+ * functions below do not read these tables. */
+int ds_deform_tables(const float* verts, int64_t nv, const int32_t* tets, int64_t T, int order, const float* dtab,
+                     const float* gw, float* sfd, float* intw, float* det, ds_stream_t stream);
+/* F[b, t*G+g, i, j] = sum_a u[b, tet[t,a], i] B[t,g,a,j] (deform.py:70-102), times intw[t*G+g] when weighted != 0.
+ * u (batch x nv x 3) f32 -> F (batch x T*G x 3 x 3) f32, 16-byte aligned. */
+int ds_deform_gradient(const float* verts, int64_t nv, const int32_t* tets, int64_t T, int order, const float* dtab,
+                       const float* gw, const float* u, int64_t batch, int weighted, float* F, ds_stream_t stream);
+/* f[b, 3 n + i] = sum over (t, a) with tet[t,a] == n, over g and j, of intw[t*G+g] P[b,t*G+g,i,j] B[t,g,a,j]
+ * (deform.py:104-125, 149-180; the reference scatters with atomics), without the intw factor when weighted == 0.
+ * P (batch x T*G x 3 x 3) f32, 16-byte aligned -> f (batch x 3 nv) f32.  inc_ptr (nv + 1), inc (T*N) int32: the
+ * node -> t*N + a incidence list in CSR form, the order of a node's entries is the order of its sum.  work: batch *
+ * T * N * 3 floats (the per-element forces between the two passes). */
+int ds_deform_force(const float* verts, int64_t nv, const int32_t* tets, int64_t T, int order, const float* dtab,
+                    const float* gw, const int32_t* inc_ptr, const int32_t* inc, const float* P, int64_t batch,
+                    int weighted, float* work, float* f, ds_stream_t stream);
 
 #ifdef __cplusplus
 }
