@@ -27,6 +27,16 @@ described.  For a custom model
        anisotropic tangent is not built (``stiff_func`` works, and ``lobpcg_func(obj.stiff_func, obj.mass_matrix, ...)``
        takes a callable).
   get_undamped_freqs  is the reference's formula, lambda + diag(U^T stiff_func(U)) - lambda m, with U = U_hat.float().
+
+Tangent models.  A model with a ``tangent()`` method (and no ``lame``) opts into the eigendecomposition with a general
+constant tangent: ``tangent()`` returns the 9x9 d vec(P) / d vec(F) (row 3i+j, column 3k+l), ``elastic_tangent`` checks
+that it is a valid elasticity tensor (finite, major and minor symmetry, positive definite Voigt matrix), and
+``HipModalOps.set_tangent`` forms K_ab = C : H_ab from the geometry tensors the assembly already holds
+(csrc/tangent.hip).  ``get_undamped_freqs`` is lambda + <C(theta), Q> - lambda m with the strain-energy moment tensors
+Q_m (``HipModalOps.tangent_forms``) computed once per eigendecomposition: u^T K(C) u = <C, Q> exactly, so autograd
+reaches the model's parameters through an 81-term dot product per mode.  ``stiff_func`` stays the matrix-free chain
+above.  ``TrainableOrthotropic`` and ``fixed_tangent`` are such models.  The geometry gradient of ``get_vals`` is not
+built for them (ds_geometry_grad is written for (lam, mu)).
 """
 import numpy as np
 import torch
@@ -139,6 +149,153 @@ def isotropic_lame(C, rtol=1e-5):
     return lam, mu
 
 
+class _TangentStress(torch.autograd.Function):
+    """vec(P) = C vec(F) on (..., 9) rows in F's dtype, with the gradient on C summed in fp64: its 81 entries are sums over
+    every Gauss point of every column (batch * T * G rows), which a float32 product loses digits on."""
+
+    ROWS = 1 << 18  # rows per fp64 slice of the backward
+
+    @staticmethod
+    def forward(ctx, F9, C):
+        Cf = C.to(F9.device, F9.dtype)
+        ctx.save_for_backward(F9, Cf)
+        ctx.c_like = (C.device, C.dtype)
+        return F9 @ Cf.transpose(0, 1)
+
+    @staticmethod
+    def backward(ctx, g):
+        F9, Cf = ctx.saved_tensors
+        gF = g @ Cf if ctx.needs_input_grad[0] else None
+        gC = None
+        if ctx.needs_input_grad[1]:
+            g2, f2 = g.reshape(-1, 9), F9.reshape(-1, 9)
+            gC = torch.zeros((9, 9), dtype=torch.float64, device=g.device)
+            for r0 in range(0, g2.shape[0], _TangentStress.ROWS):
+                gC += g2[r0:r0 + _TangentStress.ROWS].double().transpose(0, 1) @ f2[r0:r0 + _TangentStress.ROWS].double()
+            gC = gC.to(*ctx.c_like)
+        return gF, gC
+
+
+def _tangent_stress(F, C):
+    return _TangentStress.apply(F.reshape(*F.shape[:-2], 9), C).reshape(F.shape)
+
+
+_VOIGT_ROWS = (0, 4, 8, 5, 2, 1)  # 3i+j of (ij) = 11, 22, 33, 23, 13, 12
+_VOIGT_OF = (0, 5, 4, 5, 1, 3, 4, 3, 2)  # the Voigt index of 3i+j
+
+
+def elastic_tangent(C, rtol=1e-5):
+    """Validate a 9x9 tangent d vec(P) / d vec(F) (row 3i+j, column 3k+l) for the eigensolver and return it as fp64
+    NumPy, symmetrised exactly.  ValueError names the failed condition:
+      (i)   81 finite entries, max|C| > 0;
+      (ii)  major symmetry C_ijkl = C_klij within rtol * max|C| - without it K is not symmetric;
+      (iii) minor symmetry C_ijkl = C_ijlk within rtol * max|C| - without it rotations are not in K's null space and the
+            analytic rigid-mode deflation would be wrong;
+      (iv)  the 6x6 Voigt matrix of C is positive definite (a Cholesky factorisation succeeds).
+    ``rtol`` is a test of form, as ``isotropic_lame``'s: the margin is for a model whose parameters are fp32."""
+    C = np.asarray(C.detach().cpu() if isinstance(C, torch.Tensor) else C, dtype=np.float64)
+    if C.size != 81:
+        raise ValueError(f"elastic_tangent: shape: a 9x9 tangent (81 entries) expected, got shape {C.shape}")
+    C = C.reshape(9, 9)
+    if not np.isfinite(C).all():
+        raise ValueError("elastic_tangent: finite: the tangent has entries that are not finite")
+    scale = float(np.abs(C).max())
+    if scale == 0.0:
+        raise ValueError("elastic_tangent: zero: max|C| = 0")
+    C4 = C.reshape(3, 3, 3, 3)
+    major = float(np.abs(C4 - C4.transpose(2, 3, 0, 1)).max())
+    if major > rtol * scale:
+        raise ValueError(f"elastic_tangent: major symmetry C_ijkl = C_klij broken by {major:.3e} against max|C| = "
+                         f"{scale:.3e}: K would not be symmetric")
+    minor = max(float(np.abs(C4 - C4.transpose(0, 1, 3, 2)).max()), float(np.abs(C4 - C4.transpose(1, 0, 2, 3)).max()))
+    if minor > rtol * scale:
+        raise ValueError(f"elastic_tangent: minor symmetry C_ijkl = C_ijlk broken by {minor:.3e} against max|C| = "
+                         f"{scale:.3e}: rotations would not be in the null space of K")
+    # exact symmetrisation: (ij), then (kl), then the pairs - every step is a commutative two-term mean
+    C4 = 0.5 * (C4 + C4.transpose(1, 0, 2, 3))
+    C4 = 0.5 * (C4 + C4.transpose(0, 1, 3, 2))
+    C4 = 0.5 * (C4 + C4.transpose(2, 3, 0, 1))
+    C = np.ascontiguousarray(C4.reshape(9, 9))
+    voigt = C[np.ix_(_VOIGT_ROWS, _VOIGT_ROWS)]
+    try:
+        np.linalg.cholesky(voigt)
+    except np.linalg.LinAlgError:
+        raise ValueError("elastic_tangent: positive definite: the 6x6 Voigt matrix of the tangent has no Cholesky "
+                         f"factor (smallest eigenvalue {float(np.linalg.eigvalsh(voigt)[0]):.3e})") from None
+    return C
+
+
+class TrainableOrthotropic(nn.Module):
+    """Orthotropic linear elasticity with nine trainable engineering constants E1, E2, E3, nu12, nu13, nu23, G12, G13,
+    G23 (``NAMES``), each its initial value times exp(log_scale[i]).  They start at the isotropic values of ``mat``
+    (E, nu, G = E / (2 (1 + nu))), so at zero ``log_scale`` the tangent is the shipped isotropic one.  ``axes``: a 3x3
+    rotation whose columns are the material axes in the mesh's frame (default: identity)."""
+
+    NAMES = ("E1", "E2", "E3", "nu12", "nu13", "nu23", "G12", "G13", "G23")
+
+    def __init__(self, mat: Material, axes=None):
+        super().__init__()
+        E, nu = float(mat.youngs), float(mat.poisson)
+        G = E / (2 * (1 + nu))
+        self.register_buffer("initial", torch.tensor([E, E, E, nu, nu, nu, G, G, G], dtype=torch.float64))
+        self.register_buffer("axes", torch.eye(3, dtype=torch.float64) if axes is None
+                             else torch.as_tensor(axes, dtype=torch.float64).reshape(3, 3).clone())
+        self.log_scale = nn.Parameter(torch.zeros(9, dtype=torch.float64))
+        self.mat = mat
+
+    def constants(self):
+        """The nine engineering constants (fp64, autograd to ``log_scale``), in the order of ``NAMES``."""
+        return self.initial * torch.exp(self.log_scale)
+
+    def tangent(self):
+        """9x9 d vec(P) / d vec(F) in fp64 with autograd to ``log_scale``: the inverse of the 6x6 compliance, expanded
+        with both minor symmetries and rotated by ``axes``."""
+        E1, E2, E3, n12, n13, n23, G12, G13, G23 = self.constants().unbind(0)
+        zero = torch.zeros((), dtype=torch.float64, device=E1.device)
+        S = torch.stack([torch.stack([1 / E1, -n12 / E1, -n13 / E1, zero, zero, zero]),
+                         torch.stack([-n12 / E1, 1 / E2, -n23 / E2, zero, zero, zero]),
+                         torch.stack([-n13 / E1, -n23 / E2, 1 / E3, zero, zero, zero]),
+                         torch.stack([zero, zero, zero, 1 / G23, zero, zero]),
+                         torch.stack([zero, zero, zero, zero, 1 / G13, zero]),
+                         torch.stack([zero, zero, zero, zero, zero, 1 / G12])])
+        Cv = torch.linalg.inv(S)
+        Cv = 0.5 * (Cv + Cv.transpose(0, 1))
+        idx = torch.tensor(_VOIGT_OF, device=Cv.device)
+        C4 = Cv[idx][:, idx].reshape(3, 3, 3, 3)
+        R = self.axes
+        return torch.einsum("ia,jb,kc,ld,abcd->ijkl", R, R, R, R, C4).reshape(9, 9)
+
+    def forward(self, F):
+        """P = C : F."""
+        return _tangent_stress(F, self.tangent())
+
+    def jacobian_F(self):
+        return self.tangent().detach().reshape(1, 3, 3, 1, 3, 3)
+
+
+def fixed_tangent(C):
+    """A material-model class whose ``tangent()`` is the constant 9x9 tangent C (row 3i+j, column 3k+l):
+    ``DiffSoundObj(..., mat_model=fixed_tangent(C))``."""
+    C64 = torch.as_tensor(np.asarray(C.detach().cpu() if isinstance(C, torch.Tensor) else C, dtype=np.float64)).reshape(9, 9).clone()
+
+    class FixedTangent(nn.Module):
+        def __init__(self, mat: Material):
+            super().__init__()
+            self.register_buffer("C", C64.clone())
+            self.mat = mat
+
+        def tangent(self):
+            return self.C
+
+        def forward(self, F):
+            return _tangent_stress(F, self.C)
+
+        def jacobian_F(self):
+            return self.C.detach().reshape(1, 3, 3, 1, 3, 3)
+
+    return FixedTangent
+
+
 def build_model(mesh_dir, mode_num, order, mat, task, vertices=None, tets=None, scale_range=None, init_scale=None):
     """reference :98-113."""
     if task == "material" or task == "mat_baseline":
@@ -237,6 +394,11 @@ class DiffSoundObj:
     def _custom_material(self):
         return not hasattr(self.material_model, "lame")
 
+    @property
+    def _tangent_model(self):
+        """A model with ``tangent()`` and no ``lame``: the eigendecomposition with a general tangent."""
+        return self._custom_material and hasattr(self.material_model, "tangent")
+
     def _current_lame(self):
         if self._custom_material:  # the tangent at F = 0, as the reference's assembly reads it (:190)
             return isotropic_lame(self.material_model.jacobian_F().reshape(9, 9).double())
@@ -255,6 +417,14 @@ class DiffSoundObj:
 
     def update_stiff_matrix(self, assemble_batch_size=None):
         """K = lam K_lambda + mu K_mu for the current material (reference :184-220)."""
+        if self._tangent_model:  # validated on the host before anything is launched
+            C = elastic_tangent(self.material_model.tangent())
+            if self._ops is None or self._ops.sys is not self.system:
+                self._ops = HipModalOps(self.system, tangent=C)
+            else:
+                self._ops.set_tangent(C)
+            self._sparse_cache.clear()
+            return
         lam, mu = self._current_lame()
         if self._ops is None or self._ops.sys is not self.system:
             self._ops = HipModalOps(self.system, lam, mu)
@@ -267,8 +437,10 @@ class DiffSoundObj:
         ``stiff_matrix`` / ``mass_matrix`` as torch sparse tensors)."""
         if which not in self._sparse_cache:
             s = self.system
-            lam, mu = self._ops.lame if self._ops is not None else self._current_lame()
-            if which == "K":
+            if which == "K" and self._ops is not None and self._ops.lame is None:  # a tangent: the blocks of C : H
+                blocks = self._ops.k64c.reshape(-1, 3, 3)
+            elif which == "K":
+                lam, mu = self._ops.lame if self._ops is not None else self._current_lame()
                 blocks = (lam * s.klam + mu * s.kmu).reshape(-1, 3, 3)
             else:
                 blocks = s.ms[:, None, None] * torch.eye(3, dtype=torch.float64, device=s.device)
@@ -299,6 +471,7 @@ class DiffSoundObj:
         """Name kept for drop-in compatibility; runs the device-resident block eigensolver."""
         ops = self._ops
         solver = ModalSolver(ops, self.solver_config)
+        solver.vector_forms = True  # (the quadratic forms below belong to the fp32 vectors U_hat is made of)
         res = solver.solve(self.mode_num, X0=self._warm)
         self._warm = res.block_vectors
         self.last_result = res
@@ -308,12 +481,23 @@ class DiffSoundObj:
         rigid = self.system.rows_to_external(ops.rigid[:, :6]).double()
         self.U_hat_full = torch.cat([rigid, self.U_hat], dim=1)
         self._a, self._b, self._m = res.a_lambda, res.b_mu, res.m_diag
+        if self._tangent_model:
+            # Q and m of the SAME fp32 vectors: the bracket <C, Q> - lambda m is then second order in their error
+            # (an fp64 refinement returns fp64 vectors: their fp32 rounding, what U_hat.float() holds)
+            V = res.vectors.float().contiguous()
+            self._Q = ops.tangent_forms(V)
+            MV = torch.empty(V.shape, dtype=torch.float64, device=V.device)
+            ops._spmm(3, ops.sys.ms, V, MV)
+            self._m = (V.double() * MV).sum(0)
 
     # ------------------------------------------------------------------ differentiable read-outs
     def get_undamped_freqs(self):
         """(mode_num, 1) float32; gradient -> material parameters (reference :371-388)."""
         pred = self.eigenvalues
-        if self.task != "gt" and self._custom_material:  # the reference's matrix-free bracket (:381-387)
+        if self.task != "gt" and self._tangent_model:  # lambda + <C(theta), Q> - lambda m: autograd through torch alone
+            C = self.material_model.tangent().to(device=pred.device, dtype=torch.float64)
+            pred = pred + (C * self._Q).sum((-1, -2)) - pred * self._m
+        elif self.task != "gt" and self._custom_material:  # the reference's matrix-free bracket (:381-387)
             U = self.U_hat.float()
             pred = pred + (U * self.stiff_func(U)).sum(0) - pred * self._m
         elif self.task != "gt":
@@ -324,6 +508,13 @@ class DiffSoundObj:
 
     def get_vals(self):
         """lambda + diag(U^T K U) - lambda diag(U^T M U), (mode_num, 1) float32 (reference :390-399)."""
+        if self._tangent_model:
+            if self.tetmesh.vertices.requires_grad:
+                raise NotImplementedError("diffsound_amd: get_vals() of a tangent model has no gradient to the vertices: "
+                                          "the geometry gradient (ds_geometry_grad) is written for (lam, mu), and that of an "
+                                          "anisotropic tangent is not built")
+            C = self.material_model.tangent().detach().to(device=self.eigenvalues.device, dtype=torch.float64)
+            return (self.eigenvalues + (C * self._Q).sum((-1, -2)) - self.eigenvalues * self._m).float().unsqueeze(1)
         lam, mu = self._ops.lame
         pred = (self.eigenvalues + (lam * self._a + mu * self._b) - self.eigenvalues * self._m).float().unsqueeze(1)
         if self.tetmesh.vertices.requires_grad:  # geometry tasks: gradient -> vertices

@@ -671,6 +671,11 @@ class ModalSolver:
     # ``ModalResult.block_vectors`` - the whole converged block, rotated to its Ritz basis: what a warm start of the next solve takes.
     # A caller that starts every solve cold switches it off and saves one (n x b) update per solve.
     keep_block = True
+    # ``ModalResult.a_lambda / b_mu / m_diag`` as the fp64 quadratic forms of the fp32 ``vectors`` the result RETURNS (one more
+    # walk of the pattern per term, ``ops.vector_forms``) instead of those of the exact combination of the block that the vectors
+    # are the fp32 rounding of: the two differ by that rounding, 2^-24 per entry.  DiffSoundObj switches it on - its callers read
+    # the forms together with U_hat -; the hypothesis lanes keep the forms the polish has for free.
+    vector_forms = False
 
     def __init__(self, ops, cfg: Optional[SolverConfig] = None, precond=None, precond_object=None):
         """precond: optional callable (R, W) -> None writing the preconditioned residual into W
@@ -1516,6 +1521,9 @@ class ModalSolver:
         a = qs[0]
         bq = qs[1] if len(GK) > 1 else None
         m = qs[-1]
+        if self.vector_forms and hasattr(ops, "vector_forms"):
+            forms, m = ops.vector_forms(U)
+            a, bq = forms[0], (forms[1] if len(forms) > 1 else None)
         Xb = None
         if self.keep_block or self.cfg.refine_tol > 0.0:  # (the whole rotated block: a warm start's or the refinement's input)
             Xb = torch.empty_like(X)

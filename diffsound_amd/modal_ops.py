@@ -3,7 +3,8 @@
 ``TetSystem``   one mesh (topology + geometry): symbolic BSR-3 pattern, then K_lambda, K_mu, M_s
                 assembled on the GPU in fp64 (reference DiffSoundObj.update_stiff_matrix /
                 update_mass_matrix, src/diffelastic/diff_model.py:184-312).
-``HipModalOps`` one material hypothesis (lam, mu) on a TetSystem: fp32 K = lam K_lambda + mu K_mu,
+``HipModalOps`` one material hypothesis on a TetSystem - (lam, mu): fp32 K = lam K_lambda + mu K_mu, or a general 9 x 9
+                tangent C (``set_tangent``): K_ab = C : H_ab on the same geometry tensors -,
                 block-Jacobi blocks, rigid-body basis, and every large operation the solver
                 needs, each one a call into libdiffsound_hip.so.
 No operation here has a CPU implementation; tensors must be HIP tensors.
@@ -1076,6 +1077,21 @@ class _HipBlockOps:
     def rigid64(self):
         return None
 
+    def vector_forms(self, U):
+        """([u^T K_i u], u^T M u) of every column of the fp32 block U, (k,) fp64 each, for the terms of ``polish_terms()``:
+        fp64 values, fp64 products and sums.  The forms of exactly the vectors handed in."""
+        kterms, (mkind, mvals) = self.polish_terms()
+        k = U.shape[1]
+        pad = (-k) % 4
+        Up = U.contiguous() if not pad else torch.cat([U, torch.zeros((U.shape[0], pad), dtype=U.dtype, device=U.device)], 1).contiguous()
+        Y = self._scratch("vector_forms", Up.shape, torch.float64)
+        U64 = Up.double()
+        out = []
+        for kind, vals in [(kd, v) for kd, v, _ in kterms] + [(mkind, mvals)]:
+            self._spmm(kind, vals, Up, Y)
+            out.append((U64 * Y).sum(0)[:k].clone())
+        return out[:-1], out[-1]
+
     # ------------------------------------------------------------------ fp64 polish
     def polish_products(self, X):
         """fp64 Gram matrices of the terms of K and of M on the block X (fp64 values, fp64
@@ -1133,9 +1149,12 @@ class HipModalOps(_HipBlockOps):
     # the same for the ONE-level polynomial of an ord-1 mesh's operator object (no corner-node level): 8 or 0
     one_level_group_jacobi = 0
 
-    def __init__(self, system: TetSystem, lam, mu, two_level=None, _level=0, mfma_groups=None, mfma32=None, coarse_group_jacobi=None,
-                 one_level_group_jacobi=None):
-        """two_level: build the corner-node level for the two-level preconditioner (ord-2 meshes; default on)."""
+    def __init__(self, system: TetSystem, lam=None, mu=None, two_level=None, _level=0, mfma_groups=None, mfma32=None,
+                 coarse_group_jacobi=None, one_level_group_jacobi=None, tangent=None):
+        """two_level: build the corner-node level for the two-level preconditioner (ord-2 meshes; default on).
+        tangent: a 9 x 9 tangent d vec(P) / d vec(F) in the place of (lam, mu) (``set_tangent``)."""
+        if (tangent is None) == (lam is None or mu is None):
+            raise ValueError("HipModalOps: give either (lam, mu) or tangent=C")
         self.sys = system
         self._level_tag = min(int(_level), 1)
         if coarse_group_jacobi is not None:
@@ -1161,7 +1180,7 @@ class HipModalOps(_HipBlockOps):
             if lvl is not None:
                 self._xfer = lvl
                 self.coarse = HipModalOps(lvl["sys"], lam, mu, two_level=False, _level=1, mfma_groups=self.mfma_groups,
-                                          mfma32=self.mfma32, coarse_group_jacobi=self.coarse_group_jacobi)
+                                          mfma32=self.mfma32, coarse_group_jacobi=self.coarse_group_jacobi, tangent=tangent)
         G = self.mfma_groups[min(_level, 1)]
         if G not in (0, 8):
             raise ValueError("mfma_groups: 8 nodes per wavefront, or 0 for the VALU kernel")
@@ -1178,7 +1197,10 @@ class HipModalOps(_HipBlockOps):
             m4 = system.mfma_tables(MF32_G, MF32_BATCH)
             if m4["max_entries"] <= 256 and m4["max_batch_blocks"] <= MF32_BATCH * MF32_G:  # what ds_spmm_union32m serves
                 self._mfma32 = m4
-        self.set_material(lam, mu)
+        if tangent is None:
+            self.set_material(lam, mu)
+        else:
+            self.set_tangent(tangent)
         self.rigid = self._rigid_basis() if _level == 0 else None
         self._rigid_generation = getattr(system, "geometry_generation", 0)
 
@@ -1214,6 +1236,9 @@ class HipModalOps(_HipBlockOps):
         """What the solver's cached norm probe (random block, ||M G0|| / ||G0||) is valid for: this system's geometry."""
         return (id(self.sys), getattr(self.sys, "geometry_generation", 0))
 
+    k64c = None     # tangent mode: (nnzb, 9) fp64, the blocks of K = C : H as ds_combine_tangent wrote them
+    tangent = None  # tangent mode: the 9 x 9 fp64 tangent (host array); None for a (lam, mu) material
+
     def set_material(self, lam, mu):
         s = self.sys
         if self.coarse is not None:
@@ -1224,11 +1249,63 @@ class HipModalOps(_HipBlockOps):
         gen = getattr(s, "geometry_generation", 0)
         regen = getattr(self, "_rigid_generation", gen) != gen
         p = _hip.ptr
+        if self.tangent is not None:  # (the solver's kept norm probe of a tangent has no per-term products)
+            self._norm_probe = None
         self.lame = (float(lam), float(mu))
+        self.tangent = self.k64c = None
         self._k64 = self._k64grp = self._m64grp = None  # (a combined fp64 K array of the previous material must never outlive it)
         _hip.check(self._L.ds_combine_material(p(s.klam), p(s.kmu), p(s.ms), s.nnzb, p(s.diagidx), s.nv,
                                                float(lam), float(mu), p(self.k32), p(self.k32t), p(self.ms32),
                                                p(self.dinv), _hip.stream_ptr()), "ds_combine_material")
+        self._after_combine(regen, gen)
+
+    def set_tangent(self, C):
+        """K = C : H for a 9 x 9 tangent d vec(P) / d vec(F) (row 3i+j, column 3k+l; fp64, host tensor or array) in the place of
+        lam K_lambda + mu K_mu: ds_combine_tangent, then what ``set_material`` does after its combine step.  The caller
+        validates C (diffelastic.diff_model.elastic_tangent: both symmetries, a positive definite Voigt matrix)."""
+        C = np.ascontiguousarray(C.detach().cpu().numpy() if isinstance(C, torch.Tensor) else C, dtype=np.float64)
+        if C.shape != (9, 9) or not np.isfinite(C).all():
+            raise ValueError(f"set_tangent: a finite 9 x 9 tangent expected, got shape {C.shape}")
+        s = self.sys
+        if self.coarse is not None:
+            self.coarse.set_tangent(C)
+        gen = getattr(s, "geometry_generation", 0)
+        regen = getattr(self, "_rigid_generation", gen) != gen
+        p = _hip.ptr
+        if self.tangent is None:  # (the solver's kept norm probe of a (lam, mu) material holds K_lambda G0 and K_mu G0)
+            self._norm_probe = None
+        self.lame = None
+        self.tangent = C.copy()
+        self._k64 = self._k64grp = self._m64grp = None
+        if self.k64c is None:
+            self.k64c = torch.empty((s.nnzb, 9), dtype=torch.float64, device=self.device)
+        _hip.check(self._L.ds_combine_tangent(p(s.klam), p(s.ms), s.nnzb, p(s.diagidx), s.nv, C.ctypes.data, p(self.k64c),
+                                              p(self.k32), p(self.k32t), p(self.ms32), p(self.dinv), _hip.stream_ptr()),
+                   "ds_combine_tangent")
+        self._after_combine(regen, gen)
+
+    def tangent_forms(self, U):
+        """(m, 9, 9) fp64: Q[c][3i+j][3k+l] = sum_ab u_a,i H_ab[j][l] u_b,k of every column of the fp32 block U (n x m, the
+        system's internal node order), so that u^T K(C) u = (C * Q[c]).sum() for any tangent C (ds_tangent_forms)."""
+        _hip.require_gpu(U)
+        if U.dim() != 2 or U.shape[0] != self.n or U.dtype != torch.float32 or U.shape[1] < 1:
+            raise ValueError("tangent_forms: an (n x m) float32 block with m >= 1 expected")
+        if U.stride(1) != 1:
+            U = U.contiguous()
+        s, m = self.sys, U.shape[1]
+        Q = torch.empty((m, 9, 9), dtype=torch.float64, device=self.device)
+        need = self._L.ds_tangent_forms_workspace_bytes(s.nv, m)
+        ws = self._scratch("tangent_forms_ws", ((need + 7) // 8,), torch.float64)
+        p = _hip.ptr
+        _hip.check(self._L.ds_tangent_forms(p(s.rowptr), p(s.colidx), p(s.klam), s.nv, p(U), _ld(U), m, p(Q), p(ws),
+                                            ws.numel() * 8, _hip.stream_ptr()), "ds_tangent_forms")
+        return Q
+
+    def _after_combine(self, regen, gen):
+        """What follows the combine step of ``set_material`` / ``set_tangent``: everything below reads k32 / k32t / ms32 and
+        knows nothing of the material."""
+        s = self.sys
+        p = _hip.ptr
         if s.groups is not None:
             if self.kgrp is None:
                 self.kgrp = torch.empty((s.nnzb, 9), dtype=torch.float32, device=self.device)
@@ -1291,6 +1368,8 @@ class HipModalOps(_HipBlockOps):
         return Y32.contiguous()
 
     def polish_terms(self):
+        if self.lame is None:  # tangent mode: one term, the blocks ds_combine_tangent wrote
+            return [(2, self.k64c, 1.0)], (3, self.sys.ms)
         lam, mu = self.lame
         return [(2, self.sys.klam, lam), (2, self.sys.kmu, mu)], (3, self.sys.ms)
 

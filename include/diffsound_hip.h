@@ -26,6 +26,7 @@
 #ifndef DIFFSOUND_HIP_H
 #define DIFFSOUND_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -40,7 +41,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 38
+#define DS_ABI_VERSION 39
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -852,6 +853,29 @@ int ds_deform_gradient(const float* verts, int64_t nv, const int32_t* tets, int6
 int ds_deform_force(const float* verts, int64_t nv, const int32_t* tets, int64_t T, int order, const float* dtab,
                     const float* gw, const int32_t* inc_ptr, const int32_t* inc, const float* P, int64_t batch,
                     int weighted, float* work, float* f, ds_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * A general constant tangent on the assembled geometry tensors (csrc/tangent.hip, ABI 39).  The reference assembles
+ * A^T B A for any 9 x 9 B = jacobian_F() (src/diffelastic/diff_model.py:184-220); here klam of ds_assemble_kml already
+ * holds H_ab[j][l] = integral dN_a/dx_j dN_b/dx_l of every block slot, and with vec(F) row 3i+j (:207-211)
+ *   K_ab[i][k] = sum_jl C[3i+j][3k+l] H_ab[j][l].
+ * ---------------------------------------------------------------------------------------------- */
+/* The per-material step for a tangent C (81 doubles on the HOST, row 3i+j, column 3k+l; passed to the kernels by value):
+ * k64 (nnzb x 9, may be NULL) = C : H in fp64, one fixed summation order; k32 = its fp32 rounding; k32t (may be NULL) =
+ * k32 with every 3x3 block transposed; ms32 = (float)ms; dinv32 (nv x 9) = the fp32 inverse of the fp64 diagonal blocks
+ * (identity for a node no element references), as the isotropic combine step computes it.  nnzb < 2^31. */
+int ds_combine_tangent(const double* klam, const double* ms, int64_t nnzb, const int32_t* diagidx, int64_t nv,
+                       const double* C, double* k64, float* k32, float* k32t, float* ms32, float* dinv32,
+                       ds_stream_t stream);
+/* Strain-energy moment tensors of the columns of U (3 nv x m fp32, row-major, leading dimension ldu >= m, 4-byte aligned):
+ *   Q[c][3i+j][3k+l] = sum_a sum_{b in row a} u_a,i H_ab[j][l] u_b,k     (m x 81 fp64),
+ * so that u_c^T K(C) u_c = sum of C .* Q[c] for every tangent C.  fp64 arithmetic on the BSR pattern (rowptr, colidx,
+ * klam); two stages in a fixed order and no atomics: two calls give the same bits, and a column's Q does not depend on
+ * the other columns of the call.  1 <= m <= DS_TANGENT_FORMS_MAX_COLS.  work: scratch of the stated size, 8-byte aligned. */
+#define DS_TANGENT_FORMS_MAX_COLS 589815
+size_t ds_tangent_forms_workspace_bytes(int64_t nv, int m);
+int ds_tangent_forms(const int32_t* rowptr, const int32_t* colidx, const double* klam, int64_t nv, const float* U,
+                     int64_t ldu, int m, double* Q, void* work, size_t work_bytes, ds_stream_t stream);
 
 #ifdef __cplusplus
 }
