@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 39  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 40  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -106,6 +106,7 @@ _SIGNATURES = {
     "ds_deform_tables": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _P, _P, _P]),
     "ds_deform_gradient": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _I64, _I, _P, _P]),
     "ds_deform_force": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P]),
+    "ds_geometry_grad_tangent": (_I, [_P, _I64, _I, _I64, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "ds_combine_tangent": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "ds_tangent_forms_workspace_bytes": (ctypes.c_size_t, [_I64, _I]),
     "ds_tangent_forms": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _P, _P, ctypes.c_size_t, _P]),

@@ -36,7 +36,15 @@ that it is a valid elasticity tensor (finite, major and minor symmetry, positive
 Q_m (``HipModalOps.tangent_forms``) computed once per eigendecomposition: u^T K(C) u = <C, Q> exactly, so autograd
 reaches the model's parameters through an 81-term dot product per mode.  ``stiff_func`` stays the matrix-free chain
 above.  ``TrainableOrthotropic`` and ``fixed_tangent`` are such models.  The geometry gradient of ``get_vals`` is not
-built for them (ds_geometry_grad is written for (lam, mu)).
+built for them (ds_geometry_grad is written for (lam, mu)); ``get_vals_differentiable`` has it.
+
+Joint read-out.  In the reference both read-outs are differentiable in the vertices AND the material parameters at once
+(:390-399 through ``stiff_matrix`` / ``mass_matrix`` of :184-220, :222-312; :371-388 through ``stiff_func``, the Deform
+tables and ``transform_matrix``).  ``get_vals_differentiable`` is that bracket, lambda + u^T K(theta, x) u - lambda u^T
+M(x) u, as ONE autograd node over (vertices, C or (lam, mu)): the material gradient is sum_i g_i Q_i (or g.a, g.b), the
+vertex gradient comes from ds_geometry_grad_tangent (csrc/geomgrad.hip: any tangent, no atomics).
+``get_undamped_freqs`` goes through it when the vertices require a gradient, so a shape - or a shape and a material
+together - can be fitted through the oscillator and the spectral loss, for orthotropic models too.
 """
 import numpy as np
 import torch
@@ -44,7 +52,7 @@ import torch.nn as nn
 
 from ..ddsp.oscillator import WeightedParam
 from ..lobpcg.modal_solver import ModalSolver, SolverConfig, tuned_config
-from ..modal_ops import HipModalOps, TetSystem
+from ..modal_ops import HipModalOps, TetSystem, isotropic_tangent
 from .material_model import Material, MatSet
 from .mesh import TetMesh
 
@@ -329,6 +337,47 @@ class _GetVals(torch.autograd.Function):
         return grad.to(obj.tetmesh.vertices.dtype), None, None
 
 
+class _Bracket(torch.autograd.Function):
+    """bracket_i = lambda_i + u_i^T K(theta, x) u_i - lambda_i u_i^T M(x) u_i with detached (lambda_i, u_i), as one node
+    over (vertices, material): ``mat`` is the 9 x 9 tangent C, or the pair (lam, mu).  Forward from the quadratic forms of
+    the last eigendecomposition (Q, or a and b, and m).  Backward: sum_i g_i Q_i (or g.a, g.b) to the material, and to the
+    vertices ds_geometry_grad_tangent with gk = g, gm = g * lambda and the detached C of the forward."""
+
+    @staticmethod
+    def forward(ctx, vertices, obj, *mat):
+        ev, dev = obj.eigenvalues, obj.eigenvalues.device
+        if len(mat) == 1:
+            ctx.forms = (obj._Q,)
+            ctx.C = mat[0].detach().cpu().double().numpy().reshape(9, 9).copy()
+            form = (mat[0].detach().to(device=dev, dtype=torch.float64) * obj._Q).sum((-1, -2))
+        else:
+            lam, mu = (x.detach().to(device=dev, dtype=torch.float64) for x in mat)
+            ctx.forms = (obj._a, obj._b)
+            ctx.C = isotropic_tangent(float(lam), float(mu))
+            form = lam * obj._a + mu * obj._b
+        ctx.sys, ctx.ev, ctx.vectors = obj.system, ev, obj.last_result.vectors
+        ctx.like = [(x.device, x.dtype, x.shape) for x in mat]
+        ctx.vdtype = vertices.dtype
+        return (ev + form - ev * obj._m).unsqueeze(1)
+
+    @staticmethod
+    def backward(ctx, gout):
+        g = gout.reshape(-1).double()
+        gv = None
+        if ctx.needs_input_grad[0]:
+            V = ctx.vectors.float().contiguous()  # the fp32 vectors the forms belong to
+            gv = ctx.sys.geometry_grad_tangent(V, g, g * ctx.ev, ctx.C).to(ctx.vdtype)
+        gmat = []
+        for k, (dev, dtype, shape) in enumerate(ctx.like):
+            if not ctx.needs_input_grad[2 + k]:
+                gmat.append(None)
+            elif len(ctx.like) == 1:
+                gmat.append((g[:, None, None] * ctx.forms[0]).sum(0).reshape(shape).to(device=dev, dtype=dtype))
+            else:
+                gmat.append((g * ctx.forms[k]).sum().reshape(shape).to(device=dev, dtype=dtype))
+        return (gv, None, *gmat)
+
+
 class DiffSoundObj:
     def __init__(self, vertices=None, tets=None, mode_num=16, mat=MatSet.Ceramic, order=1, mat_model=FixedLinear,
                  task=None, mesh_dir=None, solver_config=None):
@@ -491,10 +540,24 @@ class DiffSoundObj:
             self._m = (V.double() * MV).sum(0)
 
     # ------------------------------------------------------------------ differentiable read-outs
+    def get_vals_differentiable(self):
+        """The bracket lambda + u^T K(theta, x) u - lambda u^T M(x) u of the last eigendecomposition, (mode_num, 1) float64,
+        with gradient to the material parameters and, when ``tetmesh.vertices.requires_grad``, to the vertices - both at
+        once, as in the reference (:371-399).  For the shipped (lam, mu) models and for tangent models."""
+        if self._custom_material and not self._tangent_model:
+            raise NotImplementedError("diffsound_amd: get_vals_differentiable() needs a model with lame() or tangent(): the "
+                                      "joint vertex / material read-out of a custom model whose stiffness is only known "
+                                      "through forward(F) is not built (get_undamped_freqs() reaches its parameters)")
+        mat = (self.material_model.tangent(),) if self._tangent_model else tuple(self.material_model.lame())
+        return _Bracket.apply(self.tetmesh.vertices, self, *mat)
+
     def get_undamped_freqs(self):
-        """(mode_num, 1) float32; gradient -> material parameters (reference :371-388)."""
+        """(mode_num, 1) float32; gradient -> material parameters (reference :371-388) and, when the vertices require a
+        gradient (and the model has ``lame`` or ``tangent``), to the vertices as well: ``get_vals_differentiable``."""
         pred = self.eigenvalues
-        if self.task != "gt" and self._tangent_model:  # lambda + <C(theta), Q> - lambda m: autograd through torch alone
+        if self.task != "gt" and self.tetmesh.vertices.requires_grad and (self._tangent_model or not self._custom_material):
+            pred = self.get_vals_differentiable().squeeze(1)
+        elif self.task != "gt" and self._tangent_model:  # lambda + <C(theta), Q> - lambda m: autograd through torch alone
             C = self.material_model.tangent().to(device=pred.device, dtype=torch.float64)
             pred = pred + (C * self._Q).sum((-1, -2)) - pred * self._m
         elif self.task != "gt" and self._custom_material:  # the reference's matrix-free bracket (:381-387)
@@ -507,7 +570,9 @@ class DiffSoundObj:
         return (torch.sqrt(pred) / 2 / np.pi).float().unsqueeze(1)
 
     def get_vals(self):
-        """lambda + diag(U^T K U) - lambda diag(U^T M U), (mode_num, 1) float32 (reference :390-399)."""
+        """lambda + diag(U^T K U) - lambda diag(U^T M U), (mode_num, 1) float32 (reference :390-399).  Gradient to the
+        vertices for (lam, mu) models only; ``get_vals_differentiable`` is the same bracket with gradient to the vertices
+        and the material parameters, for tangent models too."""
         if self._tangent_model:
             if self.tetmesh.vertices.requires_grad:
                 raise NotImplementedError("diffsound_amd: get_vals() of a tangent model has no gradient to the vertices: "

@@ -94,6 +94,18 @@ def morton_order(vertices):
     return torch.argsort(key, stable=True)
 
 
+def isotropic_tangent(lam, mu):
+    """The 9 x 9 tangent d vec(P) / d vec(F) (row 3i+j, column 3k+l) of P = mu (F + F^T) + lam tr(F) I, fp64 on the host
+    (reference src/diffelastic/diff_model.py:34-48)."""
+    C = np.zeros((3, 3, 3, 3), dtype=np.float64)
+    for i in range(3):
+        for j in range(3):
+            C[i, j, i, j] += mu
+            C[i, j, j, i] += mu
+            C[i, i, j, j] += lam
+    return C.reshape(9, 9)
+
+
 class TetSystem:
     def __init__(self, vertices, tets, order, density, reorder=True):
         """vertices (nv,3) float32 HIP tensor, tets (T,N) integer HIP tensor in the reference's local
@@ -146,6 +158,8 @@ class TetSystem:
                                union=dict(utab=pat.utab, ctab=pat.ctab, capb=UNION_CAP, ngroups=pat.ngroups,
                                           single=pat.single))  # single: every group is one chunk
         self._coarse = None
+        self._cinc = None  # corner_incidence(): topology only, built on first use
+        self._grad_rule = None  # the minimal gradient rule on the device, for geometry_grad_tangent
         self.assemble()
 
     def mfma_tables(self, group_nodes=8, batch=MF_BATCH):
@@ -344,6 +358,48 @@ class TetSystem:
                                                U.shape[1], p(gk.double().contiguous()), p(gm.double().contiguous()),
                                                float(lam), float(mu), p(gtab), p(gwt), gt.shape[0], p(self.mtab), p(grad),
                                                _hip.stream_ptr()), "ds_geometry_grad")
+        return grad if self.perm is None else grad[self.inv_perm]
+
+    def corner_incidence(self):
+        """(cinc_ptr (nv + 1), cinc (4 T)) int32: per node, in internal numbering, its (element * 4 + corner) incidences in
+        ascending order - a stable sort of the corner columns of ``tets`` by node.  Topology only: built once and kept."""
+        if self._cinc is None:
+            nodes = self.tets[:, list(fem_tables.CORNER_SLOTS[self.order])].long().reshape(-1)
+            cinc = torch.argsort(nodes, stable=True).to(torch.int32).contiguous()
+            ptr = torch.zeros(self.nv + 1, dtype=torch.int64, device=self.device)
+            ptr[1:] = torch.cumsum(torch.bincount(nodes, minlength=self.nv), 0)
+            self._cinc = (ptr.to(torch.int32).contiguous(), cinc)
+        return self._cinc
+
+    def geometry_grad_tangent(self, U, gk, gm, C):
+        """``geometry_grad`` for a general 9 x 9 tangent C (row 3i+j, column 3k+l; host tensor or array): d/dx sum_i gk_i
+        u_i^T K(C, x) u_i - gm_i u_i^T M u_i  ->  (nv, 3) fp64 in the caller's node numbering (ds_geometry_grad_tangent).
+        No atomics: two calls give the same bits; rows of nodes that are no element's corner are 0."""
+        _hip.require_gpu(U)
+        if U.dim() != 2 or U.shape[0] != self.n or U.dtype != torch.float32 or U.shape[1] < 1:
+            raise ValueError("geometry_grad_tangent: an (n x m) float32 block with m >= 1 expected")
+        C = np.ascontiguousarray(C.detach().cpu().numpy() if isinstance(C, torch.Tensor) else C, dtype=np.float64)
+        if C.shape != (9, 9) or not np.isfinite(C).all():
+            raise ValueError(f"geometry_grad_tangent: a finite 9 x 9 tangent expected, got shape {C.shape}")
+        if U.stride(1) != 1:
+            U = U.contiguous()
+        m = U.shape[1]
+        gk, gm = (torch.as_tensor(g, device=self.device).double().reshape(-1).contiguous() for g in (gk, gm))
+        if gk.numel() != m or gm.numel() != m:
+            raise ValueError(f"geometry_grad_tangent: gk and gm must have one entry per column of U ({m})")
+        dev = self.device
+        if self._grad_rule is None:
+            gt, gw = fem_tables.minimal_gradient_rule(self.order)
+            self._grad_rule = (torch.from_numpy(gt).to(dev), torch.from_numpy(gw).to(dev))
+        gtab, gwt = self._grad_rule
+        cptr, cinc = self.corner_incidence()
+        work = torch.empty((self.T, 12), dtype=torch.float64, device=dev)
+        grad = torch.empty((self.nv, 3), dtype=torch.float64, device=dev)
+        p = _hip.ptr
+        _hip.check(_hip.lib().ds_geometry_grad_tangent(p(self.tets), self.T, self.N, self.nv, p(self._tetgeo), p(U), _ld(U), m,
+                                                       p(gk), p(gm), C.ctypes.data, p(gtab), p(gwt), gtab.shape[0],
+                                                       p(self.mtab), p(cptr), p(cinc), p(work), p(grad), _hip.stream_ptr()),
+                   "ds_geometry_grad_tangent")
         return grad if self.perm is None else grad[self.inv_perm]
 
     # scipy views for tests / interop (host copies, in the caller's node numbering)
@@ -1300,6 +1356,13 @@ class HipModalOps(_HipBlockOps):
         _hip.check(self._L.ds_tangent_forms(p(s.rowptr), p(s.colidx), p(s.klam), s.nv, p(U), _ld(U), m, p(Q), p(ws),
                                             ws.numel() * 8, _hip.stream_ptr()), "ds_tangent_forms")
         return Q
+
+    def geometry_grad(self, U, gk, gm):
+        """d/dx sum_i gk_i u_i^T K u_i - gm_i u_i^T M u_i for the operator's CURRENT stiffness - its tangent, or after
+        ``set_material`` the tangent of (lam, mu) - on the system's current geometry: (nv, 3) fp64 in the caller's node
+        numbering (``TetSystem.geometry_grad_tangent``).  U: (n, m) float32 in the system's internal order."""
+        C = self.tangent if self.tangent is not None else isotropic_tangent(*self.lame)
+        return self.sys.geometry_grad_tangent(U, gk, gm, C)
 
     def _after_combine(self, regen, gen):
         """What follows the combine step of ``set_material`` / ``set_tangent``: everything below reads k32 / k32t / ms32 and

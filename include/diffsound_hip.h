@@ -41,7 +41,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 39
+#define DS_ABI_VERSION 40
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -574,6 +574,19 @@ int ds_geometry_grad(const int32_t* tets, int64_t T, int N, int64_t nv, const do
                      int64_t ldu, int m, const double* gk, const double* gm, double lam, double mu,
                      const double* gtab, const double* gw, int ng, const double* mtab, double* grad,
                      ds_stream_t stream);
+/* The same gradient for a general constant tangent (ABI 40; the stiffness of ds_combine_tangent, reference
+ * src/diffelastic/diff_model.py:184-220, :371-399):
+ *   grad = d/dx sum_i gk[i] u_i^T K(C, x) u_i - gm[i] u_i^T M(x) u_i ,   element energy J sum_g w_g vec(F)^T C vec(F),
+ * differentiated with dW/dvec(F) = (C + C^T) vec(F).  C: 81 doubles on the HOST, row 3i+j, column 3k+l, finite (passed to
+ * the kernel by value).  cinc_ptr (nv + 1), cinc (4 T) int32: per node its (element * 4 + corner) incidences in CSR form,
+ * ascending - the order of a node's sum; elem_work: T * 12 doubles of scratch.  grad (nv x 3) f64 is WRITTEN, not
+ * accumulated: no atomics, two calls give the same bits, nodes without a corner incidence (mid-edge nodes) get 0.
+ * 4 T < 2^31; the fp64 buffers 8-byte aligned, U 4-byte aligned.  The incidence list is the caller's statement about tets and
+ * is not validated: out-of-range entries are skipped, a list of another topology gives wrong sums without an error. */
+int ds_geometry_grad_tangent(const int32_t* tets, int64_t T, int N, int64_t nv, const double* tetgeo, const float* U,
+                             int64_t ldu, int m, const double* gk, const double* gm, const double* C, const double* gtab,
+                             const double* gw, int ng, const double* mtab, const int32_t* cinc_ptr, const int32_t* cinc,
+                             double* elem_work, double* grad, ds_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Damped-oscillator bank (reference src/ddsp/oscillator.py:113-141, 282-310):
