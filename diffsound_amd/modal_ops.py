@@ -469,9 +469,13 @@ class _HipBlockOps:
         w = -(-(-(-c // k)) // 4) * 4
         return [(c0, min(c, c0 + w)) for c0 in range(0, c, w)]
 
-    def _union_ok(self, X, *others, wide=False):
+    def _union_groups(self):
+        """The node-group tables of this level when it has neighbour-union tables and its blocks in their order, else None."""
         g = getattr(getattr(self, "sys", None), "groups", None)
-        if g is None or g.get("union") is None or self.kgrp is None or (X.shape[1] > 84 and not wide) or X.shape[1] % 4:
+        return None if (g is None or g.get("union") is None or self.kgrp is None) else g
+
+    def _union_ok(self, X, *others, wide=False):
+        if self._union_groups() is None or (X.shape[1] > 84 and not wide) or X.shape[1] % 4:
             return False
         # every operand is read / written 16 bytes at a time (blocks of 2 GB and more take the kernel's per-panel
         # descriptor variant; the dinv table and the value array stay under one descriptor: nv * 36, nnzb * 36 < 4 GB)
@@ -486,8 +490,8 @@ class _HipBlockOps:
 
     def level_desc(self, d, degree, lmax, lmin):
         """Fill a ds_level_t with this level's neighbour-union tables (None when the level has none)."""
-        g = getattr(getattr(self, "sys", None), "groups", None)
-        if g is None or g.get("union") is None or self.kgrp is None:
+        g = self._union_groups()
+        if g is None:
             return None
         u = g["union"]
         d.utab, d.ctab, d.ngroups, d.cap_blocks = (None if u.get("single") else u["utab"].data_ptr()), u["ctab"].data_ptr(), u["ngroups"], u["capb"]
@@ -562,10 +566,7 @@ class _HipBlockOps:
             return False
         d = self._tl_desc
         if d is None:
-            d = self._tl_desc = _hip.TwoLevelDesc()
-            t = self._xfer
-            d.rptr, d.rcol, d.rw = t["rptr"].data_ptr(), t["rcol"].data_ptr(), t["rw"].data_ptr()
-            d.pptr, d.pcol, d.pw = t["pptr"].data_ptr(), t["pcol"].data_ptr(), t["pw"].data_ptr()
+            d = self._tl_desc = self._transfer_desc()
         if self.level_desc(d.fine, *smooth) is None or co.level_desc(d.coarse, *coarse) is None:
             return False
         if not (Rc.stride(0) == Ec.stride(0) == Dc.stride(0) == ADc.stride(0) and
@@ -587,6 +588,13 @@ class _HipBlockOps:
 
     _tl_desc = None
 
+    def _transfer_desc(self):
+        """A ds_twolevel_t with the restriction / prolongation tables between this level and its corner-node level filled in."""
+        d, t = _hip.TwoLevelDesc(), self._xfer
+        d.rptr, d.rcol, d.rw = t["rptr"].data_ptr(), t["rcol"].data_ptr(), t["rw"].data_ptr()
+        d.pptr, d.pcol, d.pw = t["pptr"].data_ptr(), t["pcol"].data_ptr(), t["pw"].data_ptr()
+        return d
+
     def chebyshev_apply16(self, precond, R, W):
         """W <- p(T K) T R through the native one-level driver on bf16 iterates (ds_chebyshev_apply16: the launches the native
         iteration issues for the same preconditioner) for blocks of <= 84 columns; False when the level or block does not qualify."""
@@ -607,10 +615,9 @@ class _HipBlockOps:
         configuration has to stay on the Python loop (block wider than the union kernels take, a mass matrix that is
         not node-scalar, a preconditioner the driver does not know), else
         (iterations, result_in_s2, lam (b,) fp64 device, rerr (b,) fp64 device, history [(it, worst backward error)])."""
-        from .lobpcg.modal_solver import ChebyshevBlockJacobi, TwoLevelChebyshev
+        from .lobpcg.precond import ChebyshevBlockJacobi, TwoLevelChebyshev
 
-        g = getattr(getattr(self, "sys", None), "groups", None)
-        if (g is None or g.get("union") is None or self.kgrp is None or self.mgrp is None or self.m_kind != 1
+        if (self._union_groups() is None or self.mgrp is None or self.m_kind != 1
                 or b > 160 or b % 4 or ny % 4 or not self._union_ok(R, MX, MW, S[:, ny:ny + b], KS[:, :b], wide=True)):
             return None
         dev = self.device
@@ -620,10 +627,7 @@ class _HipBlockOps:
             co = self.coarse
             if co is None or precond.ops is not self:
                 return None
-            tl = _hip.TwoLevelDesc()
-            t = self._xfer
-            tl.rptr, tl.rcol, tl.rw = t["rptr"].data_ptr(), t["rcol"].data_ptr(), t["rw"].data_ptr()
-            tl.pptr, tl.pcol, tl.pw = t["pptr"].data_ptr(), t["pcol"].data_ptr(), t["pw"].data_ptr()
+            tl = self._transfer_desc()
             sm, cs = precond.smooth, precond.coarse
             if (self.level_desc(tl.fine, sm.degree, sm.lmax, sm.lmin) is None
                     or co.level_desc(tl.coarse, cs.degree, cs.lmax, cs.lmin) is None):
@@ -659,8 +663,8 @@ class _HipBlockOps:
         d.n, d.nv, d.b, d.k, d.ny = self.n, self.nv, b, k, ny
         d.maxit, d.lock, d.ortho_passes, d.rr_refresh = cfg.maxit, int(cfg.lock), cfg.ortho_passes, cfg.rr_refresh
         d.gram_exact = int(bool(self.gram_exact))
-        d.kx_fresh = int(bool(getattr(cfg, "kx_fresh", False)))
-        d.raw_rr = int(bool(getattr(cfg, "raw_rr", False)))
+        d.kx_fresh = int(bool(cfg.kx_fresh))
+        d.raw_rr = int(bool(cfg.raw_rr))
         d.tol, d.ortho_tol, d.A_norm, d.B_norm = float(tol), float(cfg.ortho_tol), A_norm, B_norm
         d.S, d.S2, d.KS, d.KS2 = S.data_ptr(), S2.data_ptr(), KS.data_ptr(), KS2.data_ptr()
         d.R, d.MX, d.MW = R.data_ptr(), MX.data_ptr(), MW.data_ptr()
@@ -681,11 +685,10 @@ class _HipBlockOps:
             need = max(self._L.ds_gram_workspace_bytes(self.n, p_, q_)
                        for p_ in range(4, m + 1, 4) for q_ in sorted(set(range(4, 2 * b + 1, 4)) | {p_}) if q_ <= 3 * b)
             self._native_ws[key] = need
-        if self._gram_ws is None or self._gram_ws.numel() < need:
-            self._gram_ws = torch.empty((need,), dtype=torch.uint8, device=dev)
+        self._gram_workspace(need)
         d.gbuf, d.cbuf, d.nrm, d.lam_dev = gbuf.data_ptr(), cbuf.data_ptr(), self._nrm.data_ptr(), lam_dev.data_ptr()
         d.gram_work, d.gram_work_bytes = self._gram_ws.data_ptr(), self._gram_ws.numel()
-        if getattr(cfg, "fused_residual", False) and getattr(cfg, "kx_fresh", False):
+        if cfg.fused_residual and cfg.kx_fresh:
             rws = self._residual_ws(b)
             d.res_work, d.res_work_bytes = rws.data_ptr(), rws.numel()
         else:
@@ -694,7 +697,7 @@ class _HipBlockOps:
         rerr_h = (ctypes.c_double * b)()
         hist_h = (ctypes.c_double * (cfg.maxit + 1))()
         d.lam, d.rerr, d.history, d.history_cap = lam_h, rerr_h, hist_h, cfg.maxit + 1
-        d.ritz_tol = float(getattr(cfg, "ritz_tol", 0.0))
+        d.ritz_tol = float(cfg.ritz_tol)
         d.wait_mode = int(getattr(self, "host_wait_mode", -1))  # (this operator object's - i.e. this lane's - own setting; -1: the process default)
         with _hip.blas_one_thread():
             _hip.check(self._L.ds_lobpcg_iterate(ctypes.byref(d), ctypes.byref(_hip.lapack_table()), _hip.stream_ptr()),
@@ -775,14 +778,19 @@ class _HipBlockOps:
         self.counts["apply_M_cols"] += X.shape[1]
 
     # ------------------------------------------------------------------ tall-skinny dense
+    def _gram_workspace(self, need):
+        """The Gram kernels' split-K workspace, grown to at least ``need`` bytes."""
+        if self._gram_ws is None or self._gram_ws.numel() < need:
+            self._gram_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        return self._gram_ws
+
     def gram(self, A, B, symmetric=False, exact=False):
         """G = A^T B in fp64.  exact=False: fp32 MFMA folded into fp64 every 48 rows (~1e-9 of |A_i||B_j| at the
         benchmark's row count, ~1e-7 on a few hundred rows); ops with gram_exact set always take the fp64 MFMA."""
         exact = exact or self.gram_exact
         p, q = A.shape[1], B.shape[1]
         need = self._L.ds_gram_workspace_bytes(self.n, p, q)
-        if self._gram_ws is None or self._gram_ws.numel() < need:
-            self._gram_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        self._gram_workspace(need)
         G = torch.empty((p, q), dtype=torch.float64, device=self.device)
         adt = DS_F64 if A.dtype == torch.float64 else DS_F32
         bdt = DS_F64 if B.dtype == torch.float64 else DS_F32
@@ -806,8 +814,7 @@ class _HipBlockOps:
             return arr, off
         (ta, p), (tb, q) = table(A_blocks), table(B_blocks)
         need = self._L.ds_gram_workspace_bytes(self.n, p, q)
-        if self._gram_ws is None or self._gram_ws.numel() < need:
-            self._gram_ws = torch.empty((need,), dtype=torch.uint8, device=self.device)
+        self._gram_workspace(need)
         G = torch.empty((p, q), dtype=torch.float64, device=self.device)
         _hip.check(self._L.ds_gram64_blocks(len(A_blocks), ctypes.addressof(ta), len(B_blocks), ctypes.addressof(tb), self.n,
                                             int(bool(symmetric)), _hip.ptr(G), _hip.ptr(self._gram_ws), self._gram_ws.numel(),

@@ -224,7 +224,7 @@ def test_lapack_table_has_a_source_without_scipy():
 
 def test_native_start_block_and_polish_match_the_python_forms():
     """ds_host_start_block / ds_host_polish (ABI 31) against the torch forms they replace on the device path
-    (lobpcg/modal_solver.py: `start` in ModalSolver.solve, `small` in ModalSolver._polish): the same Ritz values, the same
+    (lobpcg/modal_solver.py: `_start_block_transform`, `small` in ModalSolver._polish): the same Ritz values, the same
     coefficient matrices up to the sign of an eigenvector, the same quadratic forms - on a synthetic start block with a rigid
     block in front, and the explicit-route signal for a block that one sweep cannot orthonormalise."""
     import torch
@@ -249,7 +249,7 @@ def test_native_start_block_and_polish_match_the_python_forms():
     got = _hip.host_start_block(G, ny, b, 2e-6, 1.1e-16)
     assert got is not None
     lam, coef, cx, amp = got
-    # the Python form (as in ModalSolver.solve)
+    # the Python form (as in _start_block_transform)
     Gyk, Cy = G[:ny, :b], G[:ny, b:]
     A, B0 = _sym(G[ny:, :b]), _sym(G[ny:, b:])
     CtC = Cy.T @ Cy

@@ -315,3 +315,106 @@ def test_start_sweeps_are_ignored_without_a_nested_start(cube):
     b = ModalSolver(mk(), SolverConfig(block=24, lmax_cap=10.0, tol=5e-8, start_sweeps=3)).solve(16)  # (fresh operators: no warm estimate)
     assert a.iterations == b.iterations and torch.equal(a.eigenvalues, b.eigenvalues)
     assert np.abs(a.eigenvalues.numpy() / cube["ref"] - 1).max() < 1e-7
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Call traces: which ``ops`` members a solve calls, in which order, on how many columns.  Recorded once
+# (tests/golden/solver_call_traces.json) and compared for equality: restructuring the solver's host code must not change what it
+# launches.  Every case is stopped by its tracker at step 3, so no trace depends on how many pairs have converged by then.
+_TRACED = ("apply_K", "apply_M", "apply_KM", "gram", "mix", "mix_inplace", "residual", "residual_fused")
+
+
+class _RecordingOps(CpuModalOps):
+    """CpuModalOps that appends [level + member, last dimension of every tensor argument ...] to ``log`` at each traced call."""
+
+    def __init__(self, log, level, *args, **kw):
+        super().__init__(*args, **kw)
+        self.log, self.level = log, level
+
+
+def _traced(name):
+    inner = getattr(CpuModalOps, name)
+
+    def call(self, *args, **kw):
+        self.log.append([self.level + name] + [int(t.shape[-1]) for t in args + tuple(kw.values()) if torch.is_tensor(t)])
+        return inner(self, *args, **kw)
+
+    return call
+
+
+for _name in _TRACED:
+    setattr(_RecordingOps, _name, _traced(_name))
+
+
+def _recording_ops(cube, log, two_level=False, fused=False):
+    """The cube's operators with every traced call logged.  ``two_level``: with a corner-node level that implements the WHOLE
+    protocol (the Galerkin products P^T K P, P^T M P and the rigid basis of the corner nodes) - CpuModalOps' own coarse level
+    serves the V-cycle only, and a nested start solves an eigenproblem on that level."""
+    from oracle.ops_cpu import corner_embedding
+    import scipy.sparse as sp
+
+    args = (cube["Kl"], cube["Km"], cube["M3"], cube["v"], cube["lam"], cube["mu"])
+    if not two_level:
+        ops = _RecordingOps(log, "", *args)
+    else:
+        v, t = meshgen.kuhn_box(4)
+        t2 = fem.to_high_order(torch.from_numpy(v), torch.from_numpy(t).long(), 2)[1].numpy()
+        ops = _RecordingOps(log, "", *args, tets=t2)
+        P = sp.kron(corner_embedding(t2, ops.n // 3), sp.identity(3), format="csr")
+        corners = np.unique(t2[:, [0, 2, 4, 9]])
+        ops.coarse = _RecordingOps(log, "coarse.", *((P.T @ A @ P).tocsr() for A in args[:3]), cube["v"][corners], *args[4:])
+        ops.coarse.fused = fused
+    ops.fused = fused
+    return ops
+
+
+def _call_traces(cube, monkeypatch, report=None):
+    """{case: trace} of the cases below; ``report(case, solver)`` sees every finished solver (the recording script's margins)."""
+    from diffsound_amd.lobpcg import modal_solver as ms
+
+    log = []
+    for cls in (ms.ChebyshevBlockJacobi, ms.TwoLevelChebyshev):  # every preconditioner application, the nested start's included
+        def apply(self, R, W, *a, _inner=cls.apply, _name=cls.__name__, **kw):
+            log.append([getattr(self.ops, "level", "") + _name, int(R.shape[1]), int(W.shape[1])])
+            return _inner(self, R, W, *a, **kw)
+
+        monkeypatch.setattr(cls, "apply", apply)
+
+    def stop_at_3(state):
+        if state.ivars["istep"] == 3:
+            state.bvars["force_stop"] = True
+
+    cases = {
+        "solve": (dict(), dict(), "solve"),
+        "solve_nested_two_level": (dict(two_level=True), dict(nested_tol=3e-3, start_sweeps=2), "solve"),
+        "solve_basic": (dict(), dict(), "solve_basic"),
+        # ... and the same with the fused operators offered: the start block and the Ritz steps in coefficients
+        "solve_fused": (dict(fused=True), dict(), "solve"),
+        "solve_nested_two_level_fused": (dict(two_level=True, fused=True), dict(nested_tol=3e-3, start_sweeps=2), "solve"),
+    }
+    traces = {}
+    for case, (ops_kw, cfg_kw, method) in cases.items():
+        ops = _recording_ops(cube, log, **ops_kw)
+        solver = ModalSolver(ops, SolverConfig(block=24, **cfg_kw))
+        del log[:]  # (the trace is the solve's: the constructor's power iterations are not part of it)
+        res = getattr(solver, method)(16, tracker=stop_at_3)
+        assert res.iterations == 3
+        traces[case] = [list(e) for e in log]
+        if report is not None:
+            report(case, solver)
+    return traces
+
+
+def test_call_traces_equal_the_recorded_ones(cube, monkeypatch):
+    """The sequence of operator calls and preconditioner applications of ``solve`` (one-level; two-level with a nested start and
+    start sweeps; each also with the fused operators) and of ``solve_basic`` on the 4^3 ord-2 cube, k = 16, block = 24, against the
+    sequences recorded before the solver was split into phases (tests/golden/make_solver_call_traces.py)."""
+    import json
+    import os
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "solver_call_traces.json")) as f:
+        want = json.load(f)
+    got = _call_traces(cube, monkeypatch)
+    assert sorted(got) == sorted(want)
+    for case in want:
+        assert got[case] == want[case], case
