@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 40  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 41  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -66,6 +66,8 @@ _SIGNATURES = {
     "ds_spmm_union_narrow": (_I, [_I, _I, _P, _P, _I64, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _P]),
     "ds_spmm_union_km": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P]),
     "ds_union_residual": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _P, _I64, _I, _P, _I64, _P, _P, _P]),
+    "ds_union_residual_pre": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _P, _F, _P, _I64, _P, _I64, _I, _P,
+                                   _I64, _P, _P, _P]),
     "ds_mix": (_I, [_P, _I64, _I, _P, _I, _P, _I64, _I64, _F, _F, _P]),
     "ds_gram64_blocks": (_I, [_I, _P, _I, _P, _I64, _I, _P, _P, _I64, _P]),
     "ds_residual64_workspace_doubles": (_I64, [_I]),
@@ -142,6 +144,9 @@ class TwoLevelDesc(ctypes.Structure):
                 ("AD", _P), ("lda", _I64), ("Rr", _P), ("ldrr", _I64), ("Rc", _P), ("Ec", _P), ("Dc", _P), ("ADc", _P),
                 ("ldc", _I64), ("ncols", ctypes.c_int32), ("Wc", _P), ("ldwc", _I64), ("storage", ctypes.c_int32),
                 ("R16", _P), ("ldr16", _I64)]
+
+
+TL_BF16, TL_PREPARED, TL_OWN_INIT = 1, 2, 4  # DS_TL_* of include/diffsound_hip.h: the flags of ds_twolevel_t.storage
 
 
 class LapackTable(ctypes.Structure):

@@ -188,10 +188,12 @@ class _HipBlockOps:
                                             self.colidx.shape[0], m4["ngroups"], m4["max_entries"], m4["max_batch_blocks"], self.nv,
                                             pp(X), _ld(X), pp(Y), _ld(Y), X.shape[1], _hip.stream_ptr()), "ds_spmm_union32m")
 
-    def twolevel_apply(self, smooth, coarse, R, W, D, AD, Rr, Rc, Ec, Dc, ADc, Wc, R16=None):
+    def twolevel_apply(self, smooth, coarse, R, W, D, AD, Rr, Rc, Ec, Dc, ADc, Wc, R16=None, prepared=False):
         """The whole two-level V-cycle W = B R through the native driver (ds_twolevel_apply): one call instead of
         ~45 launches issued one by one.  ``smooth`` / ``coarse``: (degree, lmax, lmin) of the two Chebyshev operators.
         R16 given: every scratch block (D ... Wc, R16) is bf16 and the cycle runs on bf16 iterates (R, W stay fp32).
+        ``prepared`` (bf16 cycle): R16 and the smoother's first iterate (in D; in Wc for a degree-1 smoother) are already there -
+        residual_fused_pre wrote them - and the cycle starts at its first term; R is not read.
         Returns False (nothing done) when a level or a block does not qualify for the neighbour-union kernels."""
         co = self.coarse
         if co is None:
@@ -215,6 +217,8 @@ class _HipBlockOps:
         d.R, d.ldr, d.W, d.ldw = R.data_ptr(), R.stride(0), W.data_ptr(), W.stride(0)
         d.ncols = R.shape[1]
         _wire_cycle_scratch(d, D, AD, Rr, Wc, Rc, Ec, Dc, ADc, R16)
+        if prepared:
+            d.storage |= _hip.TL_PREPARED
         _hip.check(self._L.ds_twolevel_apply(ctypes.byref(d), _hip.stream_ptr()), "ds_twolevel_apply")
         c = R.shape[1]
         self.counts["apply_K_cols"] += c * (max(smooth[0] - 1, 0) + 1 + smooth[0])
@@ -270,6 +274,8 @@ class _HipBlockOps:
             scr = self._scratch("native_tl_fine", (5, self.n, b), sdt)  # Wc, D, AD, Rr, R16
             scc = co._scratch("native_tl_coarse", (4, co.n, b), sdt)  # Rc, Ec, Dc, ADc
             _wire_cycle_scratch(tl, scr[1], scr[2], scr[3], scr[0], scc[0], scc[1], scc[2], scc[3], scr[4] if bf else None)
+            if bf and not getattr(cfg, "residual_handoff", True):
+                tl.storage |= _hip.TL_OWN_INIT  # (the iteration's residual walk leaves this cycle its own first launch)
             tl.R = tl.W = 1  # (set per application by the driver; non-null for its argument check)
             d.twolevel = ctypes.pointer(tl)
             self.level_desc(d.level, sm.degree, sm.lmax, sm.lmin)
@@ -587,6 +593,22 @@ class _HipBlockOps:
             _hip.check(self._L.ds_union_residual(self._level_tag, *tabs, pp(self.kgrp), pp(self.mgrp), self.kgrp.shape[0], self.nv,
                                                  pp(xs), _ld(xs), pp(lam64[c0:]), pp(rs), _ld(rs), c1 - c0, pp(ws), ws.numel(),
                                                  pp(self._nrm[0, c0:]), pp(self._nrm[1, c0:]), _hip.stream_ptr()), "ds_union_residual")
+        self.counts["apply_K_cols"] += b
+        self.counts["apply_M_cols"] += b
+        return self._norms(b)
+
+    def residual_fused_pre(self, X, lam, c, R16, W1):
+        """The walk of residual_fused for an iteration whose preconditioner is the bf16 two-level cycle (ds_union_residual_pre; one
+        launch: <= 84 columns, fine level): instead of the fp32 R it writes the bf16 copy ``R16`` of R and the smoother's first
+        iterate ``W1`` = c T R (bf16), bit for bit what residual_fused followed by ds_cheb_init16 write.  Returns the norms."""
+        b = X.shape[1]
+        lam64 = lam.to(torch.float64).contiguous()
+        pp = _hip.ptr
+        ws = self._residual_ws(b)
+        _hip.check(self._L.ds_union_residual_pre(self._level_tag, *self._union_tabs(), pp(self.kgrp), pp(self.mgrp), self.kgrp.shape[0],
+                                                 self.nv, pp(X), _ld(X), pp(lam64), pp(self.dinv), float(c), pp(R16), _ld(R16), pp(W1),
+                                                 _ld(W1), b, pp(ws), ws.numel(), pp(self._nrm[0]), pp(self._nrm[1]), _hip.stream_ptr()),
+                   "ds_union_residual_pre")
         self.counts["apply_K_cols"] += b
         self.counts["apply_M_cols"] += b
         return self._norms(b)

@@ -31,6 +31,19 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
     return base + idx;
 }
 
+// One row of the first Chebyshev iterate W1 = c T R of the block-Jacobi polynomial: c (da r0 + db r1 + dc r2) on a lane's four
+// columns, (da, db, dc) the row of the node's 3 x 3 block T.  cheb_init16_kernel (precond16.hip) and the residual walk that
+// hands the cycle its inputs (spmm_union.inc, epilogue 6) both call it and must agree to the last bit, so the multiply-adds are
+// spelled out - db r1 first, then the r0 and r2 terms fused onto it, which is how the compiler contracted the plain expression
+// in cheb_init16_kernel - and nothing is left for the compiler to contract one way here and another way there.
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+__device__ __forceinline__ f32x4 cheb_first_row(float c, float da, float db, float dc, f32x4 r0, f32x4 r1, f32x4 r2) {
+    f32x4 o;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) o[k] = c * __builtin_fmaf(dc, r2[k], __builtin_fmaf(da, r0[k], db * r1[k]));
+    return o;
+}
+
 // Launch timing hook (include/diffsound_hip.h: ds_profile_stream / ds_profile_kinds / ds_profile_collect).  A scope brackets
 // the launches issued inside it with HIP events when `stream` is the registered one and `kind` is enabled - else it does
 // nothing (one relaxed load).  Kinds: DS_PROF_* of the public header; (a, b, c, d) = the launch's shape as that header lists.

@@ -443,6 +443,18 @@ struct Ctx {
         });
     }
 
+    // The same walk handing the bf16 two-level cycle its inputs instead of the fp32 R (ds_union_residual_pre; <= 84 columns):
+    // R16, and the fine smoother's first iterate in the block its first term reads (chebyshev16: D, or Wc when no term follows)
+    int residual_handoff(const float* X, int64_t ldx, int ncols) {
+        const ds_level_t& L = p->level;
+        const ds_twolevel_t& t = *p->twolevel;
+        const double theta = 0.5 * (t.fine.lmax + t.fine.lmin);
+        void* w1 = t.fine.degree >= 2 ? static_cast<void*>(t.D) : static_cast<void*>(t.Wc);
+        return ds_union_residual_pre(L.level_tag, L.utab, L.ctab, L.ngroups, L.cap_blocks, L.gent, L.kgrp, p->mgrp, L.nnzb, L.nv, X, ldx,
+                                     p->lam_dev, t.fine.dinv, (float)(1.0 / theta), t.R16, t.ldr16, w1, t.ldd, ncols, p->res_work,
+                                     p->res_work_bytes, p->nrm, p->nrm + 1024, stream);
+    }
+
     int copy_cols(float* dst, int64_t ldd, const float* src, int64_t lds_, int ncols) {
         if (ncols <= 0) return DS_OK;
         return hip(hipMemcpy2DAsync(dst, (size_t)ldd * 4, src, (size_t)lds_ * 4, (size_t)ncols * 4, (size_t)p->n,
@@ -452,11 +464,21 @@ struct Ctx {
 
     // W <- B R  (two-level V-cycle, or the one-level Chebyshev polynomial W = p(T K) T R); columns are independent: blocks wider
     // than the fused kernels take go in slices that share the scratch blocks (stream order)
-    int precond(float* R, int na, float* W, int64_t ldw) {
+    // handed >= 0: the residual walk wrote the cycle's inputs (residual_handoff) and `handed` leading columns of them have been
+    // locked since: the cycle starts at its first term, on the bf16 blocks from that column on (a multiple of 4: 8-byte steps,
+    // which is what the term kernels ask of their bf16 operands)
+    int precond(float* R, int na, float* W, int64_t ldw, int handed = -1) {
         return for_col_slices(na, [&](int c0, int c1) {
             if (p->twolevel) {
                 ds_twolevel_t d = *p->twolevel;
                 d.R = R + c0, d.ldr = p->ldr, d.W = W + c0, d.ldw = ldw, d.ncols = c1 - c0;
+                if (handed >= 0) {
+                    auto skip = [&](void* blk) { return static_cast<void*>(static_cast<uint16_t*>(blk) + handed); };
+                    d.storage |= DS_TL_PREPARED;
+                    d.R16 = skip(d.R16);
+                    if (d.fine.degree >= 2) d.D = static_cast<float*>(skip(d.D));
+                    else d.Wc = static_cast<float*>(skip(d.Wc));
+                }
                 return ds_twolevel_apply(&d, stream);
             }
             if (p->pr16)
@@ -761,6 +783,12 @@ extern "C" int ds_lobpcg_iterate(ds_lobpcg_t* p, const ds_lapack_t* lapack, ds_s
                            p->res_work_bytes >= ds_union_residual_workspace_bytes(p->level.ngroups, std::min(b, 84));
     // Rayleigh-Ritz on the raw basis: K X' must not be needed from K [X P W] (kx_fresh) and comes from the fused residual
     const bool raw = p->raw_rr && fused_res && !p->gram_exact;
+    // the residual walk hands the preconditioner its inputs: the bf16 two-level cycle with node blocks on the fine level, whose first
+    // launch would only convert R and apply the node blocks to it - nobody else reads the fp32 R on this route
+    const bool handoff = fused_res && p->twolevel && p->twolevel->storage == DS_TL_BF16 && p->twolevel->R16 &&
+                         !p->twolevel->fine.tgrp && p->twolevel->fine.dinv && p->twolevel->fine.nv == p->level.nv &&
+                         p->level.level_tag == 0;
+    bool handed = false;  // the residual in flight was launched in that form
     double worst = std::numeric_limits<double>::infinity();
     // The residual R = K X - (M X) diag(lam) of the CURRENT Ritz block and its norms: launched at the end of an iteration, right
     // behind the update that wrote the block (and once before the loop) - the host algebra that only the NEXT Ritz step needs
@@ -775,7 +803,8 @@ extern "C" int ds_lobpcg_iterate(ds_lobpcg_t* p, const ds_lapack_t* lapack, ds_s
                         "ds_lobpcg_iterate: Ritz values to device");
         if (rc_ != DS_OK) return rc_;
         if (fused_res) {  // R = K X - (M X) diag(lam) and the norms in one walk of the unions; K X, M X never reach memory
-            if ((rc_ = c.residual_fused(Xa, lds, p->R, ldr, na)) != DS_OK) return rc_;
+            handed = handoff && na <= 84;  // (one launch of the walk, one application of the cycle)
+            if ((rc_ = handed ? c.residual_handoff(Xa, lds, na) : c.residual_fused(Xa, lds, p->R, ldr, na)) != DS_OK) return rc_;
         } else {
             if ((rc_ = c.apply_M(Xa, lds, p->MX, ldr, na)) != DS_OK) return rc_;
             if ((rc_ = ds_residual(c.KS + k0, ldks, p->R, ldr, p->MX, ldr, Xa, lds, p->lam_dev, n, na, p->nrm, p->nrm + 1024,
@@ -805,9 +834,11 @@ extern "C" int ds_lobpcg_iterate(ds_lobpcg_t* p, const ds_lapack_t* lapack, ds_s
         // hard locking: converged leading columns leave the Ritz problem, the residual block and the preconditioner
         const int new_ncl = p->lock ? (nconv / 4) * 4 : 0;
         float* Ract = p->R;  // the residual columns of the pairs that stay active
+        int locked_now = 0;
         if (new_ncl > ncl) {
-            const int shift = new_ncl - ncl;
+            const int shift = locked_now = new_ncl - ncl;
             // the newly locked columns leave the residual block by a pointer offset (a multiple of 4 columns: 16-byte aligned)
+            // (the bf16 blocks of a handed-off residual by the same offset: Ctx::precond)
             // and enter the OTHER basis buffer once, here - from then on both buffers hold them (they used to be copied in
             // front of the active ones in every later iteration, and the residual block was shifted through a scratch block)
             Ract = p->R + shift;
@@ -822,7 +853,7 @@ extern "C" int ds_lobpcg_iterate(ds_lobpcg_t* p, const ds_lapack_t* lapack, ds_s
         }
         const int w0 = ny + b + npc;
         float* W = c.S + w0;
-        if ((rc = c.precond(Ract, na, W, lds)) != DS_OK) return rc;
+        if ((rc = c.precond(Ract, na, W, lds, handed ? locked_now : -1)) != DS_OK) return rc;
         const int sz = na + npc + na, nxp = na + npc;
         float* Sa = c.S + ny + ncl;
         float* KSa = c.KS + k0;

@@ -50,9 +50,9 @@ __global__ void __launch_bounds__(256)
     const int64_t r = node * 3;
     const f4 r0 = load_piece<IN32>(R, r, ldr, c0), r1 = load_piece<IN32>(R, r + 1, ldr, c0),
              r2 = load_piece<IN32>(R, r + 2, ldr, c0);
-    store_piece(W, r, ldw, c0, c * (d[0] * r0 + d[1] * r1 + d[2] * r2));
-    store_piece(W, r + 1, ldw, c0, c * (d[3] * r0 + d[4] * r1 + d[5] * r2));
-    store_piece(W, r + 2, ldw, c0, c * (d[6] * r0 + d[7] * r1 + d[8] * r2));
+    store_piece(W, r, ldw, c0, ds::cheb_first_row(c, d[0], d[1], d[2], r0, r1, r2));
+    store_piece(W, r + 1, ldw, c0, ds::cheb_first_row(c, d[3], d[4], d[5], r0, r1, r2));
+    store_piece(W, r + 2, ldw, c0, ds::cheb_first_row(c, d[6], d[7], d[8], r0, r1, r2));
     if (Rcopy) {
         store_piece(Rcopy, r, ldc, c0, r0);
         store_piece(Rcopy, r + 1, ldc, c0, r1);

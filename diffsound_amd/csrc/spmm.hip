@@ -183,6 +183,10 @@ struct ChebEpilogue {
     const float* mvals = nullptr;
     const double* lam = nullptr;
     float* nwork = nullptr;
+    // neighbour-union kernel, epilogue 6 (the residual that hands the bf16 cycle its inputs): the first Chebyshev iterate
+    // W1 = c2 T R as bf16 goes here (leading dimension in elements); the bf16 copy of R goes to Y
+    void* w1 = nullptr;
+    int64_t ldw1 = 0;
 };
 
 template <int KIND, int RS, int LPN_CT, int EPI>
@@ -962,38 +966,56 @@ extern "C" int64_t ds_union_residual_workspace_bytes(int64_t ngroups, int ncols)
     return ngroups * 2 * (int64_t)ncols * 4 + (int64_t)UN_NORM_BLOCKS * 2 * ncols * 8;
 }
 
-extern "C" int ds_union_residual(int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
-                                 const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv,
-                                 const float* X, int64_t ldx, const double* lam, float* R, int64_t ldr, int ncols, void* work,
-                                 int64_t work_bytes, double* rn2, double* xn2, ds_stream_t stream) {
-    DS_REQUIRE(ctab && gent && kgrp && mgrp && X && lam && R && work && rn2 && xn2, "ds_union_residual: null pointer");
-    DS_REQUIRE(level_tag == 0 || level_tag == 1, "ds_union_residual: level_tag must be 0 (fine) or 1 (corner-node level)");
+// (R16 == nullptr: epilogue 4, the fp32 rows of R; else epilogue 6, the bf16 cycle's inputs R16 and W1 in their place)
+static int union_residual(const char* who, int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
+                          const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv, const float* X,
+                          int64_t ldx, const double* lam, float* R, int64_t ldr, const float* dinv, float c, void* R16,
+                          int64_t ldr16, void* W1, int64_t ldw1, int ncols, void* work, int64_t work_bytes, double* rn2,
+                          double* xn2, ds_stream_t stream) {
+    const bool pre = R16 != nullptr;
+    DS_REQUIRE(ctab && gent && kgrp && mgrp && X && lam && (pre ? (W1 && dinv) : R != nullptr) && work && rn2 && xn2, "%s: null pointer", who);
+    DS_REQUIRE(level_tag == 0 || (level_tag == 1 && !pre), "%s: level_tag must be 0 (fine)%s", who, pre ? "" : " or 1 (corner-node level)");
     DS_REQUIRE(nv > 0 && ngroups == (nv + 3) / 4 && nnzb > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 84,
-               "ds_union_residual: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / 4)");
-    DS_REQUIRE(cap_blocks > 0 && cap_blocks <= UN_CAPB, "ds_union_residual: a chunk of %d blocks exceeds the LDS image", cap_blocks);
-    DS_REQUIRE(ldx >= ncols && ldr >= ncols, "ds_union_residual: leading dimension smaller than ncols");
-    DS_REQUIRE(X != R, "ds_union_residual: X and R must be different buffers");
-    DS_REQUIRE(ldx * 12 < (int64_t)PIPE_OOB && ldr * 12 < (int64_t)PIPE_OOB && nnzb * 36 < ((int64_t)1 << 32),
-               "ds_union_residual: operand beyond the descriptor range");
-    const uintptr_t al = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(R) | (uintptr_t)(ldx * 4) | (uintptr_t)(ldr * 4) |
-                         reinterpret_cast<uintptr_t>(kgrp) | reinterpret_cast<uintptr_t>(ctab) | reinterpret_cast<uintptr_t>(work);
-    DS_REQUIRE((al & 15) == 0, "ds_union_residual: rows, kgrp, ctab and the workspace must be 16-byte aligned");
-    DS_REQUIRE(work_bytes >= ds_union_residual_workspace_bytes(ngroups, ncols), "ds_union_residual: workspace of %lld bytes needed",
+               "%s: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / 4)", who);
+    DS_REQUIRE(cap_blocks > 0 && cap_blocks <= UN_CAPB, "%s: a chunk of %d blocks exceeds the LDS image", who, cap_blocks);
+    uintptr_t al = reinterpret_cast<uintptr_t>(X) | (uintptr_t)(ldx * 4) | reinterpret_cast<uintptr_t>(kgrp) |
+                   reinterpret_cast<uintptr_t>(ctab) | reinterpret_cast<uintptr_t>(work);
+    if (pre) {
+        DS_REQUIRE(ldx >= ncols && ldr16 >= ncols && ldw1 >= ncols, "%s: leading dimension smaller than ncols", who);
+        DS_REQUIRE(R16 != W1 && R16 != X && W1 != X, "%s: X, R16 and W1 must be different buffers", who);
+        DS_REQUIRE(ldx * 12 < (int64_t)PIPE_OOB && nv * 36 < (int64_t)PIPE_OOB && nnzb * 36 < ((int64_t)1 << 32),
+                   "%s: operand beyond the descriptor range", who);
+        const uintptr_t al8 = reinterpret_cast<uintptr_t>(R16) | reinterpret_cast<uintptr_t>(W1) | (uintptr_t)(ldr16 * 2) | (uintptr_t)(ldw1 * 2);
+        DS_REQUIRE((al8 & 7) == 0 && (reinterpret_cast<uintptr_t>(dinv) & 3) == 0, "%s: bf16 rows must be 8-byte aligned", who);
+    } else {
+        DS_REQUIRE(ldx >= ncols && ldr >= ncols, "%s: leading dimension smaller than ncols", who);
+        DS_REQUIRE(X != R, "%s: X and R must be different buffers", who);
+        DS_REQUIRE(ldx * 12 < (int64_t)PIPE_OOB && ldr * 12 < (int64_t)PIPE_OOB && nnzb * 36 < ((int64_t)1 << 32),
+                   "%s: operand beyond the descriptor range", who);
+        al |= reinterpret_cast<uintptr_t>(R) | (uintptr_t)(ldr * 4);
+    }
+    DS_REQUIRE((al & 15) == 0, "%s: rows, kgrp, ctab and the workspace must be 16-byte aligned", who);
+    DS_REQUIRE(work_bytes >= ds_union_residual_workspace_bytes(ngroups, ncols), "%s: workspace of %lld bytes needed", who,
                (long long)ds_union_residual_workspace_bytes(ngroups, ncols));
     hipStream_t st = ds::as_stream(stream);
-    ChebEpilogue epi{nullptr, 0, nullptr, 0.f, 0.f, 0};
+    ChebEpilogue epi{nullptr, 0, pre ? dinv : nullptr, 0.f, pre ? c : 0.f, 0};
     epi.mvals = mgrp, epi.lam = lam, epi.nwork = static_cast<float*>(work);
+    epi.w1 = W1, epi.ldw1 = ldw1;
+    float* Y = pre ? static_cast<float*>(R16) : R;  // (epilogue 6: bf16 rows, leading dimension in elements)
+    const int64_t ldy = pre ? ldr16 : ldr;
     const int lpn = ncols / 4;
     int rc;
     {
     ds::ProfScope prof(stream, DS_PROF_RESID, nv, nnzb, ncols, 4 << 8);  // (the walk of the unions; the two norm reductions follow)
-#define DS_UR(L, V) rc = launch_union<L, 4, false, true, V>(utab, ctab, ngroups, cap_blocks, gent, kgrp, nnzb, nv, X, ldx, R, ldr, lpn, st, epi)
+#define DS_UR(L, E, V) rc = launch_union<L, E, false, true, V>(utab, ctab, ngroups, cap_blocks, gent, kgrp, nnzb, nv, X, ldx, Y, ldy, lpn, st, epi)
     if (lpn == 20) {
-        if (level_tag == 1) DS_UR(20, 1);
-        else DS_UR(20, 0);
+        if (pre) DS_UR(20, 6, 0);
+        else if (level_tag == 1) DS_UR(20, 4, 1);
+        else DS_UR(20, 4, 0);
     } else {
-        if (level_tag == 1) DS_UR(0, 1);
-        else DS_UR(0, 0);
+        if (pre) DS_UR(0, 6, 0);
+        else if (level_tag == 1) DS_UR(0, 4, 1);
+        else DS_UR(0, 4, 0);
     }
 #undef DS_UR
     }
@@ -1004,6 +1026,27 @@ extern "C" int ds_union_residual(int level_tag, const int32_t* utab, const int32
     union_norm_final_kernel<<<(unsigned)(2 * ncols), 256, 0, st>>>(partial, ncols, rn2, xn2);
     DS_LAUNCH_CHECK("union_norm_final_kernel");
     return DS_OK;
+}
+
+extern "C" int ds_union_residual(int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
+                                 const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv,
+                                 const float* X, int64_t ldx, const double* lam, float* R, int64_t ldr, int ncols, void* work,
+                                 int64_t work_bytes, double* rn2, double* xn2, ds_stream_t stream) {
+    return union_residual("ds_union_residual", level_tag, utab, ctab, ngroups, cap_blocks, gent, kgrp, mgrp, nnzb, nv, X, ldx, lam, R,
+                          ldr, nullptr, 0.f, nullptr, 0, nullptr, 0, ncols, work, work_bytes, rn2, xn2, stream);
+}
+
+// The same walk for an iteration preconditioned by the bf16 two-level cycle (spmm_union.inc, epilogue 6): instead of the fp32
+// R it writes the cycle's inputs - the bf16 copy R16 and the first Chebyshev iterate W1 = c T R - so that ds_twolevel_apply
+// (DS_TL_PREPARED) starts at its first term.
+extern "C" int ds_union_residual_pre(int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
+                                     const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv,
+                                     const float* X, int64_t ldx, const double* lam, const float* dinv, float c, void* R16,
+                                     int64_t ldr16, void* W1, int64_t ldw1, int ncols, void* work, int64_t work_bytes,
+                                     double* rn2, double* xn2, ds_stream_t stream) {
+    DS_REQUIRE(R16, "ds_union_residual_pre: null pointer");
+    return union_residual("ds_union_residual_pre", level_tag, utab, ctab, ngroups, cap_blocks, gent, kgrp, mgrp, nnzb, nv, X, ldx, lam,
+                          nullptr, 0, dinv, c, R16, ldr16, W1, ldw1, ncols, work, work_bytes, rn2, xn2, stream);
 }
 
 // Y = K X and Y2 = (M_s (x) I3) X of ONE block in one walk of the unions (spmm_union.inc, epilogue 5): the eigensolver's

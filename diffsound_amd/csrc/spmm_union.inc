@@ -107,7 +107,7 @@ constexpr int UN_PAD = 12;  // readable entries / blocks behind the images (>= U
 #define DS_UNION_WPB 4
 #endif
 #ifndef DS_UNION_WAVES
-// (epilogue 4 carries 16 more accumulators: 4 waves per SIMD, <= 128 registers)
+// (epilogues 4 - 6 carry 16 more accumulators: 4 waves per SIMD, <= 128 registers)
 #define DS_UNION_WAVES(EPI, BF) ((EPI) >= 4 ? 4 : 5)
 #endif
 // LVL (0: fine level, 1: corner-node level) changes nothing but the kernel's SYMBOL (see spmm_mfma.inc): the eigensolver's own
@@ -124,7 +124,8 @@ __global__ void __launch_bounds__(64 * DS_UNION_WPB) __attribute__((amdgpu_waves
     // BF: X, R0, W_prev (and Y unless OUT32) are bf16 blocks (the float pointers are reinterpreted; leading dimensions
     // in elements); a lane's piece of a row is 4 columns = 8 bytes
     static_assert(!BF || (EPI == 1 || EPI == 2), "bf16 blocks: preconditioner epilogues only");
-    static_assert(EPI >= 0 && EPI <= 5, "epilogues 0 .. 5");
+    static_assert(EPI >= 0 && EPI <= 6, "epilogues 0 .. 6");
+    static_assert(EPI != 6 || (!BF && LVL == 0), "epilogue 6: fp32 operand, fine level");
     static_assert(!(BF && BIG), "bf16 blocks stay under one descriptor");
     constexpr int EB = BF ? 2 : 4;  // bytes per element of the vector blocks
     using f4 = __attribute__((ext_vector_type(4))) float;
@@ -182,7 +183,14 @@ __global__ void __launch_bounds__(64 * DS_UNION_WPB) __attribute__((amdgpu_waves
     // block are consumed by nothing but the residual (kx_fresh), so neither goes to HBM, X' is gathered once instead of twice
     // and the separate residual pass over three blocks is gone.  Per output the K and M sums are formed exactly as epilogues 0
     // and 3 form them, so R equals the three-launch result bit for bit.
-    constexpr bool RESID = EPI == 4;
+    // EPI 6: epilogue 4 for an iteration whose preconditioner is the bf16 two-level cycle.  Same walk, same sums, same norm partials;
+    // instead of the fp32 rows of R it stores what the cycle's first launch (cheb_init16_kernel, precond16.hip) would make of them:
+    // the bf16 copy R16 (in Y, leading dimension ldy in ELEMENTS) and the first Chebyshev iterate W1 = c T R as bf16 (epi.w1 /
+    // epi.ldw1; T = the node's 3 x 3 block epi.dinv, c = epi.c2).  Nobody else reads the fp32 R on that route, so the init launch's
+    // pass over it - 143 MB written here and read back there at 80 columns - is gone.  Both values equal the two-launch result
+    // bit for bit: the same fp32 R, rounded by the same conversion, and ds::cheb_first_row on both sides.
+    constexpr bool PRE = EPI == 6;
+    constexpr bool RESID = EPI == 4 || PRE;
     // EPI 5 (round 5): the same two accumulations, both WRITTEN - Y = K X and Y2 = (M_s (x) I3) X of one block in one walk (the
     // eigensolver multiplies the raw preconditioned residuals by K and by M: one gather of W instead of two); Y2 / its leading
     // dimension travel in epi.nwork / epi.ldr.  Each product is formed exactly as epilogues 0 and 3 form it.
@@ -192,7 +200,7 @@ __global__ void __launch_bounds__(64 * DS_UNION_WPB) __attribute__((amdgpu_waves
     const float* pvp = (EPI == 1 && epi.wprev) ? epi.wprev : Y;  // where W_{k-1} is read from
     const int64_t ldpv = (EPI == 1 && epi.wprev) ? epi.ldp : ldy;
     const i4s yrsrc = make_rsrc_words(pvp, BIG ? (unsigned)(ldpv * 12) : (unsigned)(3 * nv * ldpv * EB));
-    const i4s drsrc = make_rsrc_words(epi.dinv, EPI == 1 ? (unsigned)(nv * 36) : 0u);
+    const i4s drsrc = make_rsrc_words(epi.dinv, (EPI == 1 || PRE) ? (unsigned)(nv * 36) : 0u);
     const int rpanel_bytes = (int)(epi.ldr * 3 * EB), ypanel_bytes = (int)(ldpv * 3 * EB);
     int* se = s_ent[wave];
     float* svl = s_val[wave];
@@ -463,10 +471,17 @@ __global__ void __launch_bounds__(64 * DS_UNION_WPB) __attribute__((amdgpu_waves
                     const int sx = node * panel_bytes;
                     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=v"(wv[k]) : "v"(xvoff), "s"(xrsrc), "s"(sx) : "memory");
                 }
+                if constexpr (PRE) {  // the lane's row of the node's block T
+                    const int sd = node * 36;
+                    asm volatile("buffer_load_dwordx3 %0, %1, %2, %3 offen" : "=v"(drow[k]) : "v"(dvoff), "s"(drsrc), "s"(sd) : "memory");
+                }
             }
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #pragma unroll
-            for (int k = 0; k < 2; ++k) asm volatile("" : "+v"(wv[k]));
+            for (int k = 0; k < 2; ++k) {
+                asm volatile("" : "+v"(wv[k]));
+                if constexpr (PRE) asm volatile("" : "+v"(drow[k]));
+            }
         }
         if (EPI == 1 || EPI == 2) {
             if constexpr (BF) {  // 8-byte pieces, unpacked after the wait
@@ -575,7 +590,24 @@ __global__ void __launch_bounds__(64 * DS_UNION_WPB) __attribute__((amdgpu_waves
                         nr2[c] += r[c] * r[c];
                         nx2[c] += wv[k][c] * wv[k][c];
                     }
-                    store_piece(s_, r);
+                    if constexpr (PRE) {
+                        // rows 0, 1, 2 of the node in every lane (the lane holds row g; s1 / s2 hold rows g + 1 / g + 2 mod 3)
+                        const f4 p1 = pull(r, s1), p2 = pull(r, s2);
+                        const f4 ra = g == 0 ? r : (g == 1 ? p2 : p1);
+                        const f4 rb = g == 0 ? p1 : (g == 1 ? r : p2);
+                        const f4 rc = g == 0 ? p2 : (g == 1 ? p1 : r);
+                        const f3v dr = drow[k];
+                        const f4 w = ds::cheb_first_row(epi.c2, dr[0], dr[1], dr[2], ra, rb, rc);
+                        const int64_t row = (n0 + s_) * 3 + ga;
+                        i2s* r16 = reinterpret_cast<i2s*>(reinterpret_cast<char*>(Y) + (row * ldy + c0) * 2);
+                        i2s* w16 = reinterpret_cast<i2s*>(reinterpret_cast<char*>(epi.w1) + (row * epi.ldw1 + c0) * 2);
+                        if (active) {
+                            DS_STREAM_STORE(r16, pack_bf16x4(r));
+                            DS_STREAM_STORE(w16, pack_bf16x4(w));
+                        }
+                    } else {
+                        store_piece(s_, r);
+                    }
                 } else {
                     store_piece(s_, tot);
                 }

@@ -73,9 +73,11 @@ int union16(const ds_level_t& L, int epilogue, const void* X, int64_t ldx, void*
 // The same recurrence on bf16 blocks (ds_spmm_union16): R16 is the bf16 right-hand side every term reads; the iterates
 // ping-pong between the bf16 scratch blocks A and B; the LAST term writes Wout - bf16, or fp32 when out32 (the result
 // that goes back to the solver).  Not from a guess: W_1 = T Rinit / theta, Rinit fp32 (rinit_f32: the solver's residual
-// block, whose bf16 copy is written to R16 on the way) or bf16 (then Rinit == R16).
+// block, whose bf16 copy is written to R16 on the way) or bf16 (then Rinit == R16).  prepared: R16 and W_1 (in A; in Wout when
+// no term follows) are there already - the residual walk wrote them (ds_union_residual_pre) - and the first term is the first launch.
 int chebyshev16(const ds_level_t& L, const void* Rinit, int rinit_f32, int64_t ldri, void* R16, int64_t ldr, void* Wout,
-                int64_t ldw, int out32, void* A, void* B, int64_t lds, int ncols, bool from_guess, ds_stream_t stream) {
+                int64_t ldw, int out32, void* A, void* B, int64_t lds, int ncols, bool from_guess, ds_stream_t stream,
+                bool prepared = false) {
     const double theta = 0.5 * (L.lmax + L.lmin), delta = 0.5 * (L.lmax - L.lmin);
     const double sigma1 = theta / delta;
     double rho = 1.0 / sigma1;
@@ -94,7 +96,7 @@ int chebyshev16(const ds_level_t& L, const void* Rinit, int rinit_f32, int64_t l
         if (rc != DS_OK) return rc;
         Rinit = R16, rinit_f32 = 0, ldri = ldr;
     }
-    if (!from_guess) {
+    if (!from_guess && !prepared) {
         int rc = ds_cheb_init16(Rinit, rinit_f32, ldri, terms == 0 ? Wout : cur, terms == 0 ? ldw : lds,
                                 rinit_f32 ? R16 : nullptr, ldr, L.dinv, L.nv, ncols, (float)(1.0 / theta), stream);
         if (rc != DS_OK) return rc;
@@ -125,7 +127,8 @@ int twolevel16(const ds_twolevel_t* p, ds_stream_t stream) {
         return DS_ERR_ARG;
     }
     // W1 = S R (bf16 iterates in Wc / D / AD; R16 = bf16 copy of R, written by the first step)
-    int rc = chebyshev16(p->fine, p->R, 1, p->ldr, p->R16, p->ldr16, p->Wc, p->ldwc, 0, p->D, p->AD, p->ldd, c, false, stream);
+    int rc = chebyshev16(p->fine, p->R, 1, p->ldr, p->R16, p->ldr16, p->Wc, p->ldwc, 0, p->D, p->AD, p->ldd, c, false, stream,
+                         (p->storage & DS_TL_PREPARED) != 0);
     if (rc != DS_OK) return rc;
     rc = union16(p->fine, 2, p->Wc, p->ldwc, p->Rr, p->ldrr, 0, p->R16, p->ldr16, nullptr, c, 0.f, 0.f, 0, nullptr, 0, stream);
     if (rc != DS_OK) return rc;
@@ -166,11 +169,12 @@ extern "C" int ds_twolevel_apply(const ds_twolevel_t* p, ds_stream_t stream) {
     DS_REQUIRE(p->fine.degree >= 1 && p->coarse.degree >= 1 && p->fine.lmax > p->fine.lmin && p->fine.lmin > 0.0 &&
                    p->coarse.lmax > p->coarse.lmin && p->coarse.lmin > 0.0,
                "ds_twolevel_apply: bad polynomial degrees / spectral intervals");
-    if (p->storage == 1) {
+    DS_REQUIRE((p->storage & ~(DS_TL_BF16 | DS_TL_PREPARED | DS_TL_OWN_INIT)) == 0, "ds_twolevel_apply: unknown storage flags");
+    if (p->storage & DS_TL_BF16) {
         DS_REQUIRE(p->R16 && p->ldr16 >= p->ncols && p->fine.degree >= 1, "ds_twolevel_apply: bf16 storage needs the R16 block");
         return twolevel16(p, stream);
     }
-    DS_REQUIRE(p->storage == 0, "ds_twolevel_apply: storage must be 0 (fp32) or 1 (bf16)");
+    DS_REQUIRE(!(p->storage & DS_TL_PREPARED), "ds_twolevel_apply: prepared inputs are the bf16 cycle's");
     const int c = p->ncols;
     // fine-level iterates live in the compact blocks Wc / D / AD; W is written once, by the last term of the cycle
     int rc = chebyshev(p->fine, p->R, p->ldr, p->Wc, p->ldwc, p->D, p->AD, p->ldd, c, false, stream);  // W1 = S R

@@ -49,6 +49,11 @@ class SolverConfig:
     # and its column norms in ONE walk of the neighbour unions - neither product is written, X' is gathered once instead of
     # twice, and the separate residual pass over three blocks is gone (needs kx_fresh)
     fused_residual: bool = True
+    # ... and in the native iteration, when the preconditioner is the bf16 two-level cycle with node blocks on the fine level, that
+    # walk writes the cycle's inputs - the bf16 copy of R and the smoother's first iterate - instead of the fp32 R, and the cycle
+    # starts at its first term: the same iterates bit for bit, one launch and one pass over the residual block less per iteration
+    # (False: the two launches, for comparison)
+    residual_handoff: bool = True
     # Round 5 - Rayleigh-Ritz on the RAW basis [Y X P W] (needs fused_residual): W stays as the preconditioner left it; K W and
     # M W come out of ONE walk of the unions (ops.apply_KM), [Y X P W]^T [K W | M W] out of ONE Gram launch; [Y X P] is
     # M-orthonormal, so the projected Cholesky-QR transform of W is known in coefficients only, every block of the Ritz matrix

@@ -41,7 +41,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 40
+#define DS_ABI_VERSION 41
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -250,6 +250,16 @@ int ds_union_residual(int level_tag, const int32_t* utab, const int32_t* ctab, i
                       const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv, const float* X,
                       int64_t ldx, const double* lam, float* R, int64_t ldr, int ncols, void* work, int64_t work_bytes,
                       double* rn2, double* xn2, ds_stream_t stream);
+/* The same walk when the preconditioner that follows is the bf16 two-level cycle (ABI 41; epilogue 6 of the kernel, fine level
+ * only: level_tag 0).  Instead of the fp32 R it writes what the cycle's first launch (ds_cheb_init16 on R) would write: R16, the
+ * bf16 copy of R, and W1 = c T R, the first Chebyshev iterate of the fine smoother (bf16; T = dinv, the (nv x 9) node blocks,
+ * c = 2 / (lmax + lmin)) - both bit for bit what ds_union_residual followed by ds_cheb_init16 produce; rn2 / xn2 as above.
+ * ds_twolevel_apply with DS_TL_PREPARED in its storage flags then starts at its first term.  R16 / W1: bf16 blocks, leading dimensions in elements,
+ * 8-byte aligned rows. */
+int ds_union_residual_pre(int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
+                          const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv, const float* X,
+                          int64_t ldx, const double* lam, const float* dinv, float c, void* R16, int64_t ldr16, void* W1,
+                          int64_t ldw1, int ncols, void* work, int64_t work_bytes, double* rn2, double* xn2, ds_stream_t stream);
 /* Narrow blocks (ABI 28): Y = K X (kind 0, vals = kgrp) or Y = (M_s (x) I3) X (kind 3, vals = mgrp) on <= 16 columns with the
  * lanes of a wave dealt over the union's ENTRIES instead of over the columns (ds_spmm_union keeps 6 of 64 lanes busy on an
  * 8-column block and takes as long as on 80 columns): the block power iteration of the Chebyshev interval and the operator-norm
@@ -333,12 +343,20 @@ typedef struct {
     int32_t ncols;
     float* Wc;       /* fine scratch: the cycle's iterate (compact), W itself is written once at the end */
     int64_t ldwc;    /* = ldd = lda */
-    int32_t storage; /* 0: every scratch block fp32 ; 1: every scratch block bf16 (same fields, 2-byte elements; R and W
+    int32_t storage; /* flags (ABI 41; until then the values 0 and 1 only).  Bit 0: 0: every scratch block fp32 ; 1: every scratch block bf16 (same fields, 2-byte elements; R and W
                         stay fp32): the preconditioner's iterates need no more mantissa, and its terms are bound by
-                        the bytes of their vector streams */
+                        the bytes of their vector streams.
+                        DS_TL_PREPARED (with bit 0 only): the cycle's inputs are already written (ds_union_residual_pre) - R16,
+                        and the first iterate W1 of the fine smoother in the block the polynomial's first term reads (D; Wc when
+                        fine.degree == 1) - so the cycle skips ds_cheb_init16 and R is not read at all.
+                        DS_TL_OWN_INIT: read by ds_lobpcg_iterate only - its residual walk does NOT prepare this cycle's inputs
+                        (the two launches, for comparison); without it the iteration hands them over whenever it can */
     void* R16;       /* storage 1: fine bf16 scratch for the copy of R (rows x ncols, leading dimension ldr16) */
     int64_t ldr16;
 } ds_twolevel_t;
+#define DS_TL_BF16 1
+#define DS_TL_PREPARED 2
+#define DS_TL_OWN_INIT 4
 int ds_twolevel_apply(const ds_twolevel_t* p, ds_stream_t stream);
 /* One-level form: W <- p(T K) T R with the level's degree / [lmin, lmax] (Chebyshev block-Jacobi polynomial, every term
  * one fused ds_spmm_union launch); a, b: compact scratch blocks (rows x ncols, leading dimension lds). */
@@ -486,6 +504,10 @@ typedef struct {
                                  ||K|| + lambda ||M||: a SMOOTH vector passes a loose tol (the corner-level phase of a nested start:
                                  3e-3) whatever its Rayleigh quotient is - a start block that went through the preconditioner was
                                  locked with Ritz values 2 x off (profiles/r06_start_sweeps.txt).  0: the reference's test alone */
+    /* ABI 41, no new field: with res_work, a bf16 two-level cycle on node blocks (twolevel->storage without DS_TL_OWN_INIT),
+       level_tag 0 and <= 84 active columns, the residual walk writes the cycle's bf16 inputs instead of the fp32 R
+       (ds_union_residual_pre) and the cycle starts at its first term - same iterates bit for bit, one launch and one pass over
+       the residual block less per iteration */
 } ds_lobpcg_t;
 int ds_lobpcg_iterate(ds_lobpcg_t* p, const ds_lapack_t* lapack, ds_stream_t stream);
 /* ABI 31.  Self-check of the loop's host-side dense steps with the given LAPACK table - no device involved (the CPU test suite
