@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 41  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 42  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -292,6 +292,8 @@ _SIGNATURES["ds_host_wait_mode"] = (_I, [_I])
 _SIGNATURES["ds_selftest_dense"] = (_I, [ctypes.POINTER(LapackTable), _I, _I, ctypes.c_uint, ctypes.POINTER(_D)])
 _SIGNATURES["ds_host_start_block"] = (_I, [ctypes.POINTER(LapackTable), _P, _I, _I, _D, _D, _P, _P, _P, ctypes.POINTER(_D), ctypes.POINTER(_I)])
 _SIGNATURES["ds_host_polish"] = (_I, [ctypes.POINTER(LapackTable), _I, _P, _P, _P, _I, _I, _P, _P, _P])
+_SIGNATURES["ds_host_raw_basis"] = (_I, [ctypes.POINTER(LapackTable), _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, ctypes.POINTER(_I)])
+_SIGNATURES["ds_host_rr_step"] = (_I, [ctypes.POINTER(LapackTable), _P, _I, _I, _P, _P, _P])
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 _lib = None
 
@@ -347,6 +349,31 @@ def host_polish(GK, coefs, GM, k):
         check(lib().ds_host_polish(ctypes.byref(lapack_table()), len(GK), gk.data_ptr(), cf.data_ptr(), GM.data_ptr(), b, k, E.data_ptr(),
                                    C.data_ptr(), qs.data_ptr()), "ds_host_polish")
     return E, C, qs
+
+
+def host_raw_basis(GG, Gxp, lam_locked, ny, ncl, nxp, na, ortho_tol, eps):
+    """ds_host_raw_basis on host fp64 tensors (the arguments of dense._raw_basis_transform): (G, Qw) - Qw the last na columns of
+    the Python form's Q - or None for the explicit route.  The solver does not call it: it is the native loop's own step, here to be tested."""
+    GG, Gxp, lam_locked = GG.contiguous(), Gxp.contiguous(), lam_locked.contiguous()
+    G = torch.empty((nxp + na, nxp + na), dtype=torch.float64)
+    Qw = torch.empty((ny + ncl + nxp + na, na), dtype=torch.float64)
+    route = _I(0)
+    with blas_one_thread():
+        check(lib().ds_host_raw_basis(ctypes.byref(lapack_table()), GG.data_ptr(), Gxp.data_ptr(), lam_locked.data_ptr(), ny, ncl, nxp, na,
+                                      float(ortho_tol), float(eps), G.data_ptr(), Qw.data_ptr(), ctypes.byref(route)), "ds_host_raw_basis")
+    return None if route.value else (G, Qw)
+
+
+def host_rr_step(G, na):
+    """ds_host_rr_step on a host fp64 tensor G (sz x sz): (E (na), Z1 (sz x na), Zp (sz x na)) as dense._rr_step returns them."""
+    G = G.contiguous()
+    sz = G.shape[0]
+    E = torch.empty(na, dtype=torch.float64)
+    Z1, Zp = torch.empty((sz, na), dtype=torch.float64), torch.empty((sz, na), dtype=torch.float64)
+    with blas_one_thread():
+        check(lib().ds_host_rr_step(ctypes.byref(lapack_table()), G.data_ptr(), sz, na, E.data_ptr(), Z1.data_ptr(), Zp.data_ptr()),
+              "ds_host_rr_step")
+    return E, Z1, Zp
 
 
 def check(status, what):

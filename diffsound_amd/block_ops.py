@@ -109,7 +109,8 @@ class _HipBlockOps:
     @staticmethod
     def col_slices(c):
         """Column ranges of at most 84 columns (multiples of 4, as equal as possible) that tile a c-column block: what the
-        neighbour-union kernels take per launch.  136 -> (0, 68), (68, 136); 240 -> three of 80."""
+        neighbour-union kernels take per launch.  136 -> (0, 68), (68, 136); 240 -> three of 80.  (The same rule as for_col_slices of
+        csrc/lobpcg.cpp, which tiles the native loop's products: change both or neither.)"""
         if c <= 84:
             return [(0, c)]
         k = -(-c // 84)

@@ -1,5 +1,6 @@
 """The small (<= 3b x 3b) dense algebra of the modal eigensolver - fp64, on the host - and the guard that keeps its LAPACK calls
-on one thread (lobpcg/modal_solver.py)."""
+on one thread (lobpcg/modal_solver.py).  csrc/host_dense.cpp is its twin for the native loop: the functions there carry the same
+names without the underscore, and tests/test_cabi_cpu.py checks one against the other."""
 import os
 import threading
 
@@ -177,7 +178,8 @@ def _small(fn, dev, *mats):
 
 
 def _raw_basis_transform(GG, Gxp, lam_locked, ny, ncl, nxp, na, ortho_tol, eps):
-    """Round 5, Rayleigh-Ritz on the raw basis (host, fp64; the same steps as csrc/lobpcg.cpp).  GG = [Y X P W]^T [K W | M W]
+    """Round 5, Rayleigh-Ritz on the raw basis (host, fp64; raw_basis_transform of csrc/host_dense.cpp is the same
+    algebra, without the Cholesky gate).  GG = [Y X P W]^T [K W | M W]
     ((w0 + na) x 2 na, w0 = ny + ncl + nxp columns of the M-orthonormal V = [Y | X_locked | X_active P]).  Returns (G, Q):
     G = S_a^T K S_a for S_a = [X_a P W_o] (W_o = the M-orthonormalised projection of W) and Q = S_a in coordinates of the raw
     basis - or None when a single sweep would not be enough for this W."""

@@ -139,7 +139,7 @@ class _Basis:
 
 
 def _start_block_transform(G_, ny, b, ortho_tol, eps):
-    """The start block's first Ritz step in coefficients (host, fp64; ds_host_start_block is the same algebra):
+    """The start block's first Ritz step in coefficients (host, fp64; ds_host_start_block of csrc/host_dense.cpp is the same algebra):
     G_ = [Y X0]^T [K X0 | M X0].  Returns (Ritz values, coefficients of X in [Y X0], those in X0 alone, amp) or None."""
     Gyk, Cy = G_[:ny, :b], G_[:ny, b:]
     A = _sym(G_[ny:, :b])
@@ -428,7 +428,7 @@ class ModalSolver:
         eps_ = storage_eps(dt)
         Gs = ops.gram(basis.S[:, :ny + b], KS[:, :2 * b])
         if dev.type == "cuda" and cfg.native and dt == torch.float32:
-            # (the same algebra on the host thread in ONE native call with the solver loop's LAPACK table - ds_host_start_block -
+            # (the same algebra on the host thread in ONE native call with the solver loop's LAPACK table - ds_host_start_block, csrc/host_dense.cpp -
             # instead of ~30 torch calls on 80 x 80 CPU tensors: 0.65 -> 0.3 ms per start block, two per pass; round 6)
             from .. import _hip
 
@@ -991,7 +991,7 @@ class ModalSolver:
             return E_[:k].clone(), C_, Ck_, qs
 
         if ops.device.type == "cuda" and self.cfg.native and ops.dtype == torch.float32:
-            # (ds_host_polish: the same algebra in one native call on the host thread, 1.1 -> 0.5 ms per pass; round 6)
+            # (ds_host_polish, csrc/host_dense.cpp: the same algebra in one native call on the host thread, 1.1 -> 0.5 ms per pass; round 6)
             from .. import _hip
 
             try:

@@ -41,7 +41,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 41
+#define DS_ABI_VERSION 42
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -430,7 +430,7 @@ int ds_scalar_csr_spmm16(const int32_t* rowptr, const int32_t* colidx, const flo
                          int64_t ldx, void* Y, int64_t ldy, int ncols, float beta, ds_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * The eigensolver's iteration as ONE native call (csrc/lobpcg.cpp): the loop of the reference's LOBPCG.run /
+ * The eigensolver's iteration as ONE native call (csrc/lobpcg.cpp; its dense steps: csrc/host_dense.cpp): the loop of the reference's LOBPCG.run /
  * _update_ortho (src/lobpcg/_lobpcg.py:344-376, 433-477) in the re-designed form of lobpcg/modal_solver.py - residual
  * test, hard locking, preconditioner, single-sweep projected Cholesky-QR, Rayleigh-Ritz by recurrence, basis update -
  * issued on `stream`; the <= 3b x 3b dense steps run on the calling thread with the LAPACK / BLAS routines of
@@ -528,6 +528,16 @@ int ds_host_start_block(const ds_lapack_t* lapack, const double* G, int ny, int 
                         double* coef, double* cx, double* amp, int* route);
 int ds_host_polish(const ds_lapack_t* lapack, int nterms, const double* GK, const double* coefs, const double* GM, int b, int k,
                    double* E, double* C, double* qs);
+/* ABI 42.  Two dense steps of the iteration itself, on the HOST with the caller's LAPACK table (no device), exported so that they can be
+ * checked against their Python twins of lobpcg/dense.py (_raw_basis_transform, _rr_step); row-major doubles.
+ * ds_host_raw_basis: GG = [Y X P W]^T [K W | M W] ((w0 + na) x 2 na, w0 = ny + ncl + nxp), Gxp = [X_a P]^T K [X_a P] (nxp x nxp), lam_locked
+ *   (ncl Ritz values) -> *route = 0: G ((nxp + na) x (nxp + na)) = S_a^T K S_a for S_a = [X_a P W_o], Qw ((w0 + na) x na) = W_o in the raw
+ *   basis; *route = 1 (nothing else written): eps x amp >= ortho_tol or a breakdown - the caller orthonormalises explicitly.
+ * ds_host_rr_step: G (sz x sz, sz >= 2 na) -> E (its na lowest eigenvalues), Z1 (sz x na, their vectors), Zp (sz x na, an orthonormal
+ *   basis of (I - Z1 Z1[:na]^T) E_x). */
+int ds_host_raw_basis(const ds_lapack_t* lapack, const double* GG, const double* Gxp, const double* lam_locked, int ny, int ncl, int nxp,
+                      int na, double ortho_tol, double eps, double* G, double* Qw, int* route);
+int ds_host_rr_step(const ds_lapack_t* lapack, const double* G, int sz, int na, double* E, double* Z1, double* Zp);
 /* How the host thread of ds_lobpcg_iterate waits for its stream when its descriptor says wait_mode = -1 (ABI 30; process-wide default 0).  0: hipStreamSynchronize (the
  * runtime spins when the host has more cores than devices); 1: a 20 us poll, then a sleep on an event created with
  * hipEventBlockingSync - for callers that run several solves on several streams and threads at once (the hypothesis lanes of

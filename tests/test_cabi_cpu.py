@@ -1,5 +1,6 @@
 """The C-ABI library loads on a CPU-only box and exports every symbol the header declares; the
 host-side symbolic phase (ds_pattern_*) is exercised for real (it needs no GPU)."""
+import functools
 import os
 import re
 
@@ -222,6 +223,22 @@ def test_lapack_table_has_a_source_without_scipy():
         _hip.lapack_table("netlib")
 
 
+def _synthetic_pencil(n=400, ny=16):
+    """(K, M, Y, rng): dense SPD M, symmetric positive semi-definite K and an M-orthonormal rigid block Y (6 vectors, padded with
+    zero columns to ny) with K Y = 0; rng is the generator that drew them, for what a test draws on top."""
+    rng = np.random.default_rng(5)
+    Bq = rng.standard_normal((n, n))
+    M = Bq @ Bq.T / n + np.eye(n)
+    Kq = rng.standard_normal((n, n))
+    K = Kq @ Kq.T + 5 * np.eye(n)
+    Y = np.linalg.qr(rng.standard_normal((n, 6)))[0]
+    Y = Y @ np.linalg.inv(np.linalg.cholesky(Y.T @ M @ Y)).T           # M-orthonormal rigid block, 6 vectors + 10 zero columns
+    Y = np.concatenate([Y, np.zeros((n, ny - 6))], 1)
+    K = K - K @ Y[:, :6] @ np.linalg.solve(Y[:, :6].T @ K @ Y[:, :6], Y[:, :6].T @ K)  # K Y = 0
+    K = 0.5 * (K + K.T)
+    return K, M, Y, rng
+
+
 def test_native_start_block_and_polish_match_the_python_forms():
     """ds_host_start_block / ds_host_polish (ABI 31) against the torch forms they replace on the device path
     (lobpcg/modal_solver.py: `_start_block_transform`, `small` in ModalSolver._polish): the same Ritz values, the same
@@ -232,17 +249,8 @@ def test_native_start_block_and_polish_match_the_python_forms():
     from diffsound_amd.lobpcg.modal_solver import _orthonormalizer_q, _sym
 
     _hip = _lib()
-    rng = np.random.default_rng(5)
     n, ny, b, k = 400, 16, 24, 20
-    Bq = rng.standard_normal((n, n))
-    M = Bq @ Bq.T / n + np.eye(n)
-    Kq = rng.standard_normal((n, n))
-    K = Kq @ Kq.T + 5 * np.eye(n)
-    Y = np.linalg.qr(rng.standard_normal((n, 6)))[0]
-    Y = Y @ np.linalg.inv(np.linalg.cholesky(Y.T @ M @ Y)).T           # M-orthonormal rigid block, 6 vectors + 10 zero columns
-    Y = np.concatenate([Y, np.zeros((n, ny - 6))], 1)
-    K = K - K @ Y[:, :6] @ np.linalg.solve(Y[:, :6].T @ K @ Y[:, :6], Y[:, :6].T @ K)  # K Y = 0
-    K = 0.5 * (K + K.T)
+    K, M, Y, rng = _synthetic_pencil(n, ny)
     X0 = rng.standard_normal((n, b))
     S = np.concatenate([Y, X0], 1)
     G = torch.from_numpy(np.concatenate([S.T @ K @ X0, S.T @ M @ X0], 1))
@@ -291,3 +299,100 @@ def test_native_start_block_and_polish_match_the_python_forms():
     assert torch.allclose(C.T @ _sym(GM) @ C, torch.eye(b, dtype=torch.float64), atol=1e-10)
     with pytest.raises(RuntimeError, match="not positive definite"):
         _hip.host_polish(GK, cf, GM - 10 * torch.eye(b, dtype=torch.float64), k)
+
+
+@functools.lru_cache(maxsize=None)
+def _pencil_eigenpairs():
+    """The synthetic pencil and its dense generalised eigensolve (computed once; nobody writes to the arrays): K U = M U diag(w),
+    U^T M U = I, w ascending - the first six pairs are the rigid block (w = 0 to rounding)."""
+    import scipy.linalg
+
+    K, M, Y, _ = _synthetic_pencil()
+    w, U = scipy.linalg.eigh(K, M)
+    for a in (K, M, Y, w, U):
+        a.setflags(write=False)
+    return K, M, Y, w, U
+
+
+def _raw_basis_inputs(ny, ncl, nxp, na, duplicate=False):
+    """V = [Y | X_locked | X_a P] M-orthonormal with X_locked^T K X_locked = diag(lam_locked) and K-orthogonal to the rest: X_locked
+    and X_a are consecutive eigenvectors of the pencil behind the rigid ones, P an orthonormal combination of the 3 npc vectors that
+    follow (M-orthonormal and M-, K-orthogonal to Y, X_locked and X_a).  W random; ``duplicate``: its second column is X_a's first."""
+    K, M, Y, w, U = _pencil_eigenpairs()
+    rng = np.random.default_rng(100 * ny + 10 * ncl + nxp)
+    npc = nxp - na
+    Xl, Xa = U[:, 6:6 + ncl], U[:, 6 + ncl:6 + ncl + na]
+    rest = U[:, 6 + ncl + na:6 + ncl + na + 3 * npc]
+    P = rest @ np.linalg.qr(rng.standard_normal((3 * npc, npc)))[0] if npc else rest[:, :0]
+    V = np.concatenate([Y[:, :ny], Xl, Xa, P], 1)
+    W = rng.standard_normal((K.shape[0], na))
+    if duplicate:
+        W[:, 1] = Xa[:, 0]
+    S = np.concatenate([V, W], 1)
+    XP = np.concatenate([Xa, P], 1)
+    t = torch.from_numpy
+    GG = t(np.concatenate([S.T @ K @ W, S.T @ M @ W], 1))
+    return GG, t(XP.T @ K @ XP), t(w[6:6 + ncl].copy()), t(S.T @ M @ S), t(S.T @ K @ S)
+
+
+@pytest.mark.parametrize("ny,ncl,nxp,na", [(0, 0, 8, 8), (16, 0, 16, 8), (16, 4, 24, 12), (16, 8, 8, 8)])
+def test_native_raw_basis_transform_matches_the_python_form(ny, ncl, nxp, na):
+    """ds_host_raw_basis (csrc/host_dense.cpp: raw_basis_transform, the step ds_lobpcg_iterate runs every iteration of the raw
+    route) against dense._raw_basis_transform on the synthetic pencil: without a rigid block, with P, with locked columns, and the
+    first iteration after a lock (no P).  The same route; the same G; Qw = the last na columns of the Python form's Q; and two
+    invariants that need no second implementation: with Q = [E | Qw] the active basis is M-orthonormal, Q^T (S^T M S) Q = I, and
+    G is its Ritz matrix, Q^T (S^T K S) Q, for the TRUE dense products of S = [V W].  A W with a column copied from X_a takes the
+    explicit route in both.
+    Known difference: the Python form also refuses a block whose unscaled G0 - C^T C has no Cholesky factor; the native step left
+    that gate out on purpose (the scaled factorisation inside orthonormalizer_q is its breakdown test).  The inputs here are ones
+    on which the gate does not decide: a random W is well conditioned (positive definite, the gate passes), and the copied column
+    fails the diagonal test in front of the gate.
+    Tolerances: those of test_native_start_block_and_polish_match_the_python_forms for the same algebra across the two LAPACKs."""
+    from diffsound_amd.lobpcg.dense import _raw_basis_transform
+
+    _hip = _lib()
+    ortho_tol, eps = 2e-6, 6e-8
+    GG, Gxp, lam_l, SMS, SKS = _raw_basis_inputs(ny, ncl, nxp, na)
+    with _hip.blas_one_thread():
+        got = _hip.host_raw_basis(GG, Gxp, lam_l, ny, ncl, nxp, na, ortho_tol, eps)
+        ref = _raw_basis_transform(GG, Gxp, lam_l, ny, ncl, nxp, na, ortho_tol, eps)
+    assert got is not None and ref is not None
+    (G, Qw), (G_py, Q_py) = got, ref
+    w0, sz = ny + ncl + nxp, nxp + na
+    assert G.shape == (sz, sz) and Qw.shape == (w0 + na, na)
+    assert torch.allclose(G, G_py, rtol=0, atol=1e-9 * float(G_py.abs().max()))
+    assert torch.allclose(Qw, Q_py[:, nxp:], rtol=0, atol=1e-9 * float(Q_py.abs().max()))
+    Q = torch.zeros((w0 + na, sz), dtype=torch.float64)
+    Q[ny + ncl:w0, :nxp] = torch.eye(nxp, dtype=torch.float64)
+    Q[:, nxp:] = Qw
+    assert float((Q.T @ SMS @ Q - torch.eye(sz, dtype=torch.float64)).abs().max()) < 1e-9
+    assert torch.allclose(G, Q.T @ SKS @ Q, rtol=0, atol=1e-9 * float(G.abs().max()))
+    GGd, Gxpd, lam_d, _, _ = _raw_basis_inputs(ny, ncl, nxp, na, duplicate=True)
+    with _hip.blas_one_thread():
+        assert _hip.host_raw_basis(GGd, Gxpd, lam_d, ny, ncl, nxp, na, ortho_tol, eps) is None
+        assert _raw_basis_transform(GGd, Gxpd, lam_d, ny, ncl, nxp, na, ortho_tol, eps) is None
+
+
+@pytest.mark.parametrize("sz,na", [(24, 8), (36, 12), (240, 80)])
+def test_native_rr_step_matches_the_python_form(sz, na):
+    """ds_host_rr_step (csrc/host_dense.cpp: rr_step) against dense._rr_step on G = U diag(1..sz) U^T, U random orthogonal: unit
+    spectral gaps make the wanted vectors well defined.  (240, 80) is the benchmark's shape and the only one that takes the
+    staged dsytrd / dstedc / dormtr path.  E and Z1 agree up to column signs; Zp agrees directly - Tm = I - Z1 Z1[:na]^T does not
+    depend on those signs and Cholesky-QR is unique; [Z1 Zp] has orthonormal columns.
+    Tolerances: those of test_native_start_block_and_polish_match_the_python_forms."""
+    from diffsound_amd.lobpcg.dense import _rr_step
+
+    _hip = _lib()
+    rng = np.random.default_rng(sz)
+    U = np.linalg.qr(rng.standard_normal((sz, sz)))[0]
+    G = torch.from_numpy(U @ np.diag(np.arange(1.0, sz + 1)) @ U.T)
+    with _hip.blas_one_thread():
+        E, Z1, Zp = _hip.host_rr_step(G, na)
+        E_py, Z1_py, Zp_py = _rr_step(G, na)
+    assert E.shape == (na,) and Z1.shape == (sz, na) and Zp.shape == (sz, na)
+    assert torch.allclose(E, E_py, rtol=1e-11, atol=0)
+    sign = torch.sign((Z1 * Z1_py).sum(0))
+    assert torch.allclose(Z1 * sign[None, :], Z1_py, rtol=0, atol=1e-9 * float(Z1_py.abs().max()))
+    assert torch.allclose(Zp, Zp_py, rtol=0, atol=1e-9 * float(Zp_py.abs().max()))
+    ZZ = torch.cat([Z1, Zp], 1)
+    assert float((ZZ.T @ ZZ - torch.eye(2 * na, dtype=torch.float64)).abs().max()) < 1e-9
