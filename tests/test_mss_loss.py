@@ -8,7 +8,9 @@ loss values at every scale of the reference experiments, d loss / d audio agains
 Round 5: G9 (tests/golden/g9_mss_loss.npz) holds values and gradients of the REFERENCE's own MSSLoss, run in the build
 container with torchaudio's Spectrogram supplied as a restatement of torchaudio 2.0.2 (tests/golden/_ref_harness.py): the
 reference's lines - weights, log2, eps, alpha, hop, the sum over the scales - are pinned by it on the CPU (oracle) and on the
-device (kernels); the Spectrogram underneath stays a restated third-party algorithm (torch.stft semantics)."""
+device (kernels); the Spectrogram underneath stays a restated third-party algorithm (torch.stft semantics).
+The kernels on their own - element by element through the C ABI, at hops, clip lengths and frame counts this file never uses - are
+tests/test_stft_kernels_gpu.py (GPU) and tests/test_stft_ref_cpu.py (its references and bounds, no GPU)."""
 import os
 import numpy as np
 import pytest

@@ -14,44 +14,17 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _osc_ref as R  # noqa: E402
+from _guarded import Guarded, dev as _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SR = R.SR
-PAD = 64
 TV_CASES = [(s, "base") for s in R.TV_SHAPES] + [(s, v) for s in R.TV_SHAPES if s[3] in (65, 1025) for v in R.TV_VARIANTS]
 BANK_CASES = [(s, True) for s in R.BANK_SHAPES] + [(R.BANK_SHAPES[i], False) for i in (0, 3, 5)]
 
 
 def _id(case):
     return "-".join(map(str, case[0])) + "-" + str(case[1])
-
-
-def _dev():
-    assert torch.cuda.is_available(), "needs a HIP device"
-    return torch.device("cuda:0")
-
-
-class Guarded:
-    """An output of ``shape`` placed PAD elements inside a NaN-filled buffer."""
-
-    def __init__(self, shape, dtype=torch.float32):
-        self.shape = tuple(shape)
-        self.n = int(np.prod(self.shape))
-        self.buf = torch.full((self.n + 2 * PAD,), float("nan"), dtype=dtype, device=_dev())
-
-    @property
-    def ptr(self):
-        return self.buf.data_ptr() + PAD * self.buf.element_size()
-
-    def numpy(self):
-        return self.buf[PAD:PAD + self.n].cpu().numpy().reshape(self.shape)
-
-    def check(self, what):
-        whole = self.buf.cpu().numpy()
-        assert np.isnan(whole[:PAD]).all(), f"{what}: written before its start"
-        assert np.isnan(whole[PAD + self.n:]).all(), f"{what}: written past its end"
-        assert np.isfinite(whole[PAD:PAD + self.n]).all(), f"{what}: not every element written / finite"
 
 
 def _up(x):
