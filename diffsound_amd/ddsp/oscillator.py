@@ -2,7 +2,9 @@
 
 Class names, constructor arguments, ``forward`` signatures, returned shapes/dtypes and the
 ``damped_freq`` attribute follow the reference; the (A, m, S) signal path itself is ONE fused HIP
-kernel (``ds_osc_bank_fwd`` / ``ds_osc_bank_bwd``) wrapped in a ``torch.autograd.Function``.
+kernel (``ds_osc_bank_fwd`` / ``ds_osc_bank_bwd``) wrapped in a ``torch.autograd.Function``; a force of more
+than 512 taps, or one that is itself trained (``train_forces=True``), renders through the recursive-resonator
+kernels (``ds_osc_driven_fwd`` / ``ds_osc_driven_bwd``), which also return the force gradient.
 The tiny per-mode parameter algebra (softplus-weighted bins, d = (alpha + beta w0^2)/2,
 w = sqrt(w0^2 - d^2)) stays in torch so autograd reaches every learnable leaf exactly as in the
 reference.
@@ -181,9 +183,69 @@ def oscillator_bank_tv(dmp, frq, amp, force, sample_num, sr):
     return _OscBankTV.apply(dmp, frq, amp, force, int(sample_num), float(sr))
 
 
+class _OscDriven(torch.autograd.Function):
+    """The same y as ``_OscBank`` from the recursive resonator x[t] = z (x[t-1] + force[t]) per mode (ds_osc_driven_fwd /
+    ds_osc_driven_bwd): any force length, gradients for d, w, amp and force."""
+
+    @staticmethod
+    def _work(L, A, m, S, device):
+        nbytes = L.ds_osc_driven_workspace_bytes(A, m, S)
+        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+    @staticmethod
+    def forward(ctx, d, w, amp, force, S, sr):
+        _hip.require_gpu(d, w, force, amp)
+        d = d.detach().double().contiguous()
+        w = w.detach().double().contiguous()
+        force = force.detach().float().contiguous()
+        ampc = None if amp is None else amp.detach().float().contiguous()
+        A, nF = force.shape
+        m = d.shape[0]
+        L = _hip.lib()
+        work, nbytes = _OscDriven._work(L, A, m, S, force.device)
+        y = torch.empty((A, S), dtype=torch.float32, device=force.device)
+        p = _hip.ptr
+        _hip.check(L.ds_osc_driven_fwd(p(d), p(w), p(ampc), p(force), A, m, nF, S, float(sr), p(work), nbytes, p(y),
+                                       _hip.stream_ptr()), "ds_osc_driven_fwd")
+        ctx.save_for_backward(d, w, force, ampc if ampc is not None else torch.empty(0, device=force.device))
+        ctx.has_amp = ampc is not None
+        ctx.S, ctx.sr = S, float(sr)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        d, w, force, ampc = ctx.saved_tensors
+        amp = ampc if ctx.has_amp else None
+        A, nF = force.shape
+        m = d.shape[0]
+        gy = gy.float().contiguous()
+        L = _hip.lib()
+        work, nbytes = _OscDriven._work(L, A, m, ctx.S, gy.device)
+        gd = torch.empty(m, dtype=torch.float64, device=gy.device)
+        gw = torch.empty(m, dtype=torch.float64, device=gy.device)
+        gamp = torch.empty((A, m), dtype=torch.float32, device=gy.device) if amp is not None else None
+        gforce = torch.empty((A, nF), dtype=torch.float32, device=gy.device) if ctx.needs_input_grad[3] else None
+        p = _hip.ptr
+        _hip.check(L.ds_osc_driven_bwd(p(gy), p(d), p(w), p(amp), p(force), A, m, nF, ctx.S, ctx.sr, p(work), nbytes, p(gd),
+                                       p(gw), p(gamp), p(gforce), _hip.stream_ptr()), "ds_osc_driven_bwd")
+        return gd, gw, gamp, gforce, None, None
+
+
+FIR_MAX_FORCE = 512  # taps the FIR kernels of csrc/oscillator.hip hold in LDS (MAXF)
+
+
+def oscillator_bank_driven(d, w, amp, force, sample_num, sr):
+    """``oscillator_bank`` on the recursive-resonator kernels whatever the force length (tests, measurement)."""
+    return _OscDriven.apply(d, w, amp, force, int(sample_num), float(sr))
+
+
 def oscillator_bank(d, w, amp, force, sample_num, sr):
-    """Functional entry: d, w (m,) fp64 HIP tensors (autograd ok), amp (A,m) or None, force (A,F)."""
-    return _OscBank.apply(d, w, amp, force, int(sample_num), float(sr))
+    """Functional entry: d, w (m,) fp64 HIP tensors (autograd ok), amp (A,m) or None, force (A,F), any F >= 1.
+    Up to 512 taps without a force gradient this is the FIR bank (ds_osc_bank_fwd / _bwd); a longer force, or one that
+    requires grad, goes through the driven bank (ds_osc_driven_fwd / _bwd), which also returns the force gradient."""
+    if force.shape[-1] <= FIR_MAX_FORCE and not force.requires_grad:
+        return _OscBank.apply(d, w, amp, force, int(sample_num), float(sr))
+    return _OscDriven.apply(d, w, amp, force, int(sample_num), float(sr))
 
 
 def _device_of(t):
@@ -195,22 +257,46 @@ def _device_of(t):
 
 
 class _BankBase(nn.Module):
-    def _setup(self, forces, audio_num, mode_num, sample_num, sr, mat):
+    def _setup(self, forces, audio_num, mode_num, sample_num, sr, mat, train_forces=False):
         self.audio_num = audio_num
         self.sr = sr
         self.sample_num = sample_num
         self.mode_num = mode_num
         self.mat = mat
         self.force_frame_num = forces.shape[-1]
-        self.register_buffer("_force", forces.detach().reshape(audio_num, -1).float().clone(), persistent=False)
-        # the reference keeps the time-flipped conv1d weight as ``forces`` (oscillator.py:80-82)
-        self.forces = torch.flip(forces.reshape(audio_num, 1, -1), [-1])
+        self.train_forces = bool(train_forces)
+        if self.train_forces:  # the force itself is fitted: a parameter, rendered through the driven bank
+            self.force = nn.Parameter(forces.detach().reshape(audio_num, -1).float().clone())
+        else:
+            self.register_buffer("_force", forces.detach().reshape(audio_num, -1).float().clone(), persistent=False)
+            # the reference keeps the time-flipped conv1d weight as ``forces`` (oscillator.py:80-82)
+            self.forces = torch.flip(forces.reshape(audio_num, 1, -1), [-1])
 
-    def _render(self, freq_linear, alpha, beta, amp):
-        """freq_linear (m,1) or (m,) any float dtype; alpha/beta python floats or (1,m,1) tensors; amp (A,m,1)|None."""
+    @property
+    def forces(self):
+        if self.train_forces:
+            return torch.flip(self.force.reshape(self.audio_num, 1, -1), [-1])
+        return self._forces_flipped
+
+    @forces.setter
+    def forces(self, value):
+        if self.train_forces:
+            raise AttributeError("forces is computed from the parameter ``force`` (train_forces=True)")
+        self._forces_flipped = value
+
+    def _force_on_device(self):
+        """(device, force (A, F) on it): the buffer is moved once, a trained force stays where the module was put."""
+        if self.train_forces:
+            dev = _device_of(self.force)
+            return dev, self.force.to(dev)
         dev = _device_of(self._force)
         if self._force.device != dev:
             self._force = self._force.to(dev)
+        return dev, self._force
+
+    def _render(self, freq_linear, alpha, beta, amp):
+        """freq_linear (m,1) or (m,) any float dtype; alpha/beta python floats or (1,m,1) tensors; amp (A,m,1)|None."""
+        dev, force = self._force_on_device()
         f = freq_linear.reshape(self.mode_num).to(dev).double()
         w0sq = (f * (2 * np.pi)) ** 2
         if torch.is_tensor(alpha):
@@ -222,16 +308,16 @@ class _BankBase(nn.Module):
         fd = (w / (2 * np.pi)).float()
         self.damped_freq = fd.reshape(1, self.mode_num, 1).expand(self.audio_num, self.mode_num, self.sample_num)
         a = None if amp is None else amp.reshape(self.audio_num, self.mode_num).to(dev)
-        return oscillator_bank(d, w, a, self._force, self.sample_num, self.sr)
+        return oscillator_bank(d, w, a, force, self.sample_num, self.sr)
 
 
 class TraditionalDampedOscillator(_BankBase):
     """Fixed Rayleigh damping (alpha, beta from the material), unit amplitudes
     (reference oscillator.py:246-310)."""
 
-    def __init__(self, forces, audio_num, mode_num, sample_num, sr, mat: Material):
+    def __init__(self, forces, audio_num, mode_num, sample_num, sr, mat: Material, train_forces=False):
         super().__init__()
-        self._setup(forces, audio_num, mode_num, sample_num, sr, mat)
+        self._setup(forces, audio_num, mode_num, sample_num, sr, mat, train_forces)
         self.alpha = mat.alpha
         self.beta = mat.beta
 
@@ -246,9 +332,9 @@ class DampedOscillator(_BankBase):
     """Per-mode learnable alpha/beta (64 log-spaced bins) and per-(audio, mode) amplitude
     (reference oscillator.py:49-141)."""
 
-    def __init__(self, forces, audio_num, mode_num, sample_num, sr, f_range: list, mat: Material):
+    def __init__(self, forces, audio_num, mode_num, sample_num, sr, f_range: list, mat: Material, train_forces=False):
         super().__init__()
-        self._setup(forces, audio_num, mode_num, sample_num, sr, mat)
+        self._setup(forces, audio_num, mode_num, sample_num, sr, mat, train_forces)
         bin_num = 64
         self.alpha_list = torch.exp(torch.linspace(np.log(mat.alpha / 10), np.log(mat.alpha * 10), bin_num))
         self.alpha = WeightedSum([1, mode_num, 1], list(self.alpha_list))
@@ -262,15 +348,13 @@ class DampedOscillator(_BankBase):
         return self._render(freq_linear, self.alpha(), self.beta(), self.amp())
 
     def _curve_render(self, freq_linear, damping_curve):
-        dev = _device_of(self._force)
-        if self._force.device != dev:
-            self._force = self._force.to(dev)
+        dev, force = self._force_on_device()
         f = freq_linear.reshape(self.mode_num).to(dev).double()
         d = curve_on_device(damping_curve, f.detach())  # the reference evaluates the curve on detached frequencies
         w0sq = (f * (2 * np.pi)) ** 2
         w = torch.sqrt(w0sq - d ** 2)
         self.damped_freq = (w / (2 * np.pi)).float().reshape(1, self.mode_num, 1)
-        return oscillator_bank(d, w, None, self._force, self.sample_num, self.sr)
+        return oscillator_bank(d, w, None, force, self.sample_num, self.sr)
 
     def early(self, freq_linear, damping_curve):
         """Damping per mode from ``damping_curve``, unit amplitudes, no normalisation (reference oscillator.py:85-109)."""
@@ -332,9 +416,9 @@ class GTDampedOscillator(_BankBase):
     parameter set); with ``non_linear_rate = 0`` - what the reference's callers pass - it is not touched and the
     closed-form bank renders the clip, otherwise the time-varying kernel (ds_osc_tv_fwd / ds_osc_tv_bwd) does."""
 
-    def __init__(self, forces, audio_num, mode_num, sample_num, sr, f_range: list, mat: Material):
+    def __init__(self, forces, audio_num, mode_num, sample_num, sr, f_range: list, mat: Material, train_forces=False):
         super().__init__()
-        self._setup(forces, audio_num, mode_num, sample_num, sr, mat)
+        self._setup(forces, audio_num, mode_num, sample_num, sr, mat, train_forces)
         self.freq_linear = WeightedSum([1, mode_num, 1], f_range)
         self.freq_nonlinear = WeightedSum([audio_num, mode_num, sample_num], f_range)
         bin_num = 64
@@ -363,13 +447,15 @@ class GTDampedOscillator(_BankBase):
 
     def _render_time_varying(self, rate):
         """reference :219-242 with the (A, m, S) cumsum / exp / sin / mode-sum / conv1d chain as one kernel pair."""
-        dev = _device_of(self._force)
-        if self._force.device != dev:
-            self._force = self._force.to(dev)
+        if self.force_frame_num > FIR_MAX_FORCE:
+            raise ValueError(f"time-varying render (non_linear_rate != 0): force of {self.force_frame_num} taps, the FIR "
+                             f"kernels hold at most {FIR_MAX_FORCE}; the closed-form render (non_linear_rate = 0) takes a "
+                             "force of any length")
+        dev, force = self._force_on_device()
         undamped = (self.freq_linear() + rate * self.freq_nonlinear()).to(dev)  # (A, m, S)
         lbd = (undamped * 2 * np.pi) ** 2
         damp = 0.5 * (self.alpha().to(dev) + self.beta().to(dev) * lbd)
         freq = (lbd - damp ** 2) ** 0.5 / (2 * np.pi)
         self.undamped_freq = ((2 * np.pi * freq) ** 2 + damp ** 2) ** 0.5 / (2 * np.pi)
         amp = self.amp().reshape(self.audio_num, self.mode_num).to(dev)
-        return oscillator_bank_tv(damp, freq, amp, self._force, self.sample_num, self.sr)
+        return oscillator_bank_tv(damp, freq, amp, force.detach(), self.sample_num, self.sr)

@@ -41,7 +41,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 42
+#define DS_ABI_VERSION 43
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -665,6 +665,29 @@ int ds_osc_tv_fwd(const float* dmp, const float* frq, const float* amp, const fl
 int ds_osc_tv_bwd(const float* gy, const float* dmp, const float* frq, const float* amp, const float* force, int A,
                   int m, int F, int S, double sr, float* gs, float* g_dmp, float* g_frq, float* gamp,
                   ds_stream_t stream);
+
+/* Driven bank (ABI 43): the closed-form bank above under a force of ANY length F >= 1 (F > S included), with a force
+ * gradient.  Replaces the grouped conv1d(signal, forces) of src/ddsp/oscillator.py:113-141, 282-310 where the force is a
+ * recorded one (utils.load_audio returns the Force channel of every clip) or is itself being fitted: conv1d's autograd
+ * reaches the force tensor.  Per mode the recursive resonator
+ *   x[t] = z (x[t-1] + force[t]),  z = exp((-d + i w) / sr),  x[-1] = 0,  force[t] = 0 for t >= F ;  y[a,t] = sum_m amp[a,m] Im x_m[a,t]
+ * which is  y[a,t] = sum_{j < F, j <= t} force[a,j] sum_m amp[a,m] Im z_m^(t-j+1), the y of ds_osc_bank_fwd.  Backward with
+ * l[t] = z (l[t+1] + gy[t]), l[S] = 0:  gforce[a,j] = sum_m amp Im l_m[a,j] for j < min(F, S) and exactly 0 for j >= S ;
+ * gamp[a,m] = sum_t gy Im x ;  G_m = sum_a amp sum_t x l / z (complex product),  gd = -Im G / sr,  gw = Re G / sr.
+ * d, w, amp (NULL = 1), force, y, gy, gd, gw, gamp (may be NULL): dtypes and meaning of ds_osc_bank_fwd / _bwd ; gforce
+ * (A x F) f32 or NULL.  A <= 65535.  work: ds_osc_driven_workspace_bytes(A, m, S) bytes, 16-byte aligned, scratch: the
+ * state entering every tile of 1024 samples per (clip, mode) - A m ceil(S / 1024) complex doubles, written by both calls -
+ * and A m complex doubles that only the backward writes; each call fills it itself, nothing is kept between calls.
+ * gd, gw 8-byte aligned.  fp64 states, every power z^n from exp / sincos of n d / sr, n w / sr; one fp32 rounding per
+ * sample of y, gforce, gamp.  No atomics: the same inputs give the same bits in every output and in the workspace.
+ * Asynchronous on the stream, no allocation, no synchronisation.  Refused (DS_ERR_ARG, message in ds_last_error()): a
+ * null required pointer, A, m, S or F <= 0, sr <= 0, A > 65535, work_bytes below the query, a misaligned pointer. */
+int64_t ds_osc_driven_workspace_bytes(int A, int m, int S);
+int ds_osc_driven_fwd(const double* d, const double* w, const float* amp, const float* force, int A, int m, int F, int S,
+                      double sr, void* work, int64_t work_bytes, float* y, ds_stream_t stream);
+int ds_osc_driven_bwd(const float* gy, const double* d, const double* w, const float* amp, const float* force, int A, int m,
+                      int F, int S, double sr, void* work, int64_t work_bytes, double* gd, double* gw, float* gamp /*or NULL*/,
+                      float* gforce /*or NULL, A x F*/, ds_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-scale spectral loss head (reference src/ddsp/mss_loss.py:50-62, 70-122: SSSLoss types 'l1_loss' and
