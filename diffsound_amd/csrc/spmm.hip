@@ -11,15 +11,15 @@
 // node groups share a wave.  Block values are fetched by all lanes of a group from the same
 // address (hardware broadcast).  Accumulation in registers, one store per output element.
 // Algorithmic bytes per launch: nnzb*(vals + 4) + (nv+1)*4 + 2*3nv*ncols*sizeof(T).
+//
+// This unit: the row-wise kernels, the fp64 kernels and the neighbour-union walk with its narrow and fp64 forms (spmm_union.inc,
+// spmm_narrow.inc, spmm_f64_union.inc, included below in this order, after spmm_device.h).  The matrix-core forms are units of
+// their own (spmm_mfma.hip, spmm_mfma32.hip), the launch timing hook is profile.cpp.
 #include <algorithm>
-#include <atomic>
 #include <cstdlib>
-#include <mutex>
 #include <type_traits>
-#include <vector>
 
-#include "ds_common.h"
-#include "ds_diag.h"
+#include "spmm_device.h"
 
 namespace {
 
@@ -160,34 +160,9 @@ constexpr int WN_CHUNK = 64;  // blocks of a row staged per pass
 // X panels are fetched with buffer loads: the lane's byte offset inside a 3-row panel is loop-invariant
 // (voffset) and the neighbour's panel start is a wave-uniform scalar (soffset = id * panel bytes), so the
 // per-block address arithmetic is one s_mul_i32 instead of a 64-bit multiply-add per lane.
-using f4v = __attribute__((ext_vector_type(4))) float;
 __device__ __forceinline__ f4v buf_load4(__amdgpu_buffer_rsrc_t rsrc, int voff, int soff) {
     return __builtin_bit_cast(f4v, __builtin_amdgcn_raw_buffer_load_b128(rsrc, voff, soff, 0));
 }
-
-// Optional fused epilogue (EPI = 1, KIND 0, RS 3): one term of the Chebyshev block-Jacobi polynomial,
-//   Y_i <- X_i + c1 (X_i - Y_i) + c2 T_i (R0_i - (K X)_i)        (Y holds W_{k-1} on entry, W_{k+1} on exit)
-// so a preconditioner term is ONE launch and the product K X never goes to HBM.
-struct ChebEpilogue {
-    const float* r0;
-    int64_t ldr;
-    const float* dinv;
-    float c1, c2;
-    int first;  // W_{k-1} = 0: Y is not read
-    // neighbour-union kernel only: W_{k-1} read from here instead of from Y (nullptr: from Y, the in-place form) - the
-    // last term of a polynomial run on compact scratch blocks can then land in a column range of a wider buffer
-    const float* wprev = nullptr;
-    int64_t ldp = 0;
-    // neighbour-union kernel, epilogue 4 (fused residual R = K X - (M X) diag(lam)): node-scalar mass values in group order,
-    // the Ritz values (device, fp64, one per column) and the per-group partial column norms (ngroups x 2 x ncols floats)
-    const float* mvals = nullptr;
-    const double* lam = nullptr;
-    float* nwork = nullptr;
-    // neighbour-union kernel, epilogue 6 (the residual that hands the bf16 cycle its inputs): the first Chebyshev iterate
-    // W1 = c2 T R as bf16 goes here (leading dimension in elements); the bf16 copy of R goes to Y
-    void* w1 = nullptr;
-    int64_t ldw1 = 0;
-};
 
 template <int KIND, int RS, int LPN_CT, int EPI>
 __global__ void __launch_bounds__(256)
@@ -379,8 +354,6 @@ int launch_wn(const int32_t* rowptr, const int32_t* colidx, const void* vals, co
 }
 
 #include "spmm_union.inc"
-#include "spmm_mfma.inc"
-#include "spmm_mfma32.inc"
 #include "spmm_narrow.inc"
 #include "spmm_f64_union.inc"
 
@@ -792,88 +765,6 @@ extern "C" int ds_spmm_residual(const int32_t* rowptr, const int32_t* colidx, co
 }
 
 
-// ------------------------------------------------------------------------------------------------
-// Launch timing hook (bench.py's live roofline figures): while a stream is registered with ds_profile_stream, every launch
-// of an ENABLED kind (ds_profile_kinds; default: the fused Chebyshev term only) on it is bracketed by HIP events;
-// ds_profile_collect returns the durations with the shape of each launch.  One registered stream at a time; a relaxed flag
-// keeps the cost off every other launch.
-namespace {
-struct TermRecord {
-    hipEvent_t e0, e1;
-    int64_t nv, nnzb;
-    int ncols, first;  // first | element bytes of the vector blocks << 8 | kind << 16
-};
-std::atomic<void*> g_prof_stream{nullptr};
-std::atomic<unsigned> g_prof_kinds{1u};
-std::mutex g_prof_mutex;
-std::vector<TermRecord> g_prof_records;
-size_t g_prof_cap = 0;
-}  // namespace
-
-ds::ProfScope::ProfScope(ds_stream_t stream, int kind, int64_t a, int64_t b, int c, int d) {
-    if (stream == nullptr || g_prof_stream.load(std::memory_order_relaxed) != stream) return;
-    if (!((g_prof_kinds.load(std::memory_order_relaxed) >> kind) & 1u)) return;
-    std::lock_guard<std::mutex> lock(g_prof_mutex);
-    if (g_prof_records.size() >= g_prof_cap) return;
-    auto* r = new TermRecord{nullptr, nullptr, a, b, c, (d & 0xffff) | (kind << 16)};
-    if (hipEventCreate(&r->e0) != hipSuccess) {
-        delete r;
-        return;
-    }
-    if (hipEventCreate(&r->e1) != hipSuccess) {
-        (void)hipEventDestroy(r->e0);
-        delete r;
-        return;
-    }
-    st_ = ds::as_stream(stream);
-    (void)hipEventRecord(r->e0, st_);
-    rec_ = r;
-}
-
-ds::ProfScope::~ProfScope() {
-    if (!rec_) return;
-    auto* r = static_cast<TermRecord*>(rec_);
-    (void)hipEventRecord(r->e1, st_);
-    std::lock_guard<std::mutex> lock(g_prof_mutex);
-    g_prof_records.push_back(*r);
-    delete r;
-}
-
-extern "C" int ds_profile_kinds(unsigned mask) {
-    g_prof_kinds.store(mask ? mask : 1u);
-    return DS_OK;
-}
-
-extern "C" int ds_profile_stream(ds_stream_t stream, int64_t capacity) {
-    std::lock_guard<std::mutex> lock(g_prof_mutex);
-    for (auto& r : g_prof_records) {
-        (void)hipEventDestroy(r.e0);
-        (void)hipEventDestroy(r.e1);
-    }
-    g_prof_records.clear();
-    g_prof_cap = capacity > 0 ? (size_t)capacity : 0;
-    g_prof_stream.store(capacity > 0 ? stream : nullptr);
-    return DS_OK;
-}
-
-extern "C" int64_t ds_profile_collect(float* ms, int64_t* nv, int64_t* nnzb, int32_t* ncols, int32_t* first, int64_t cap) {
-    std::lock_guard<std::mutex> lock(g_prof_mutex);
-    g_prof_stream.store(nullptr);
-    int64_t n = 0;
-    for (auto& r : g_prof_records) {
-        if (n < cap && hipEventSynchronize(r.e1) == hipSuccess) {
-            float t = 0.f;
-            if (hipEventElapsedTime(&t, r.e0, r.e1) == hipSuccess) {
-                ms[n] = t, nv[n] = r.nv, nnzb[n] = r.nnzb, ncols[n] = r.ncols, first[n] = r.first;
-                ++n;
-            }
-        }
-        (void)hipEventDestroy(r.e0);
-        (void)hipEventDestroy(r.e1);
-    }
-    g_prof_records.clear();
-    return n;
-}
 
 extern "C" int ds_spmm_union(int epilogue, int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
                              const int32_t* gent,
@@ -1132,174 +1023,6 @@ extern "C" int ds_spmm_union16(int epilogue, const int32_t* utab, const int32_t*
 #undef DS_U16
 }
 
-// ------------------------------------------------------------------------------------------------
-// MFMA form of the bf16 preconditioner terms (spmm_mfma.inc)
-extern "C" int ds_pack_kc(const float* k32, const int32_t* kperm, int64_t nnzb, void* kc, ds_stream_t stream) {
-    DS_REQUIRE(k32 && kperm && kc && nnzb > 0, "ds_pack_kc: bad argument");
-    DS_REQUIRE((reinterpret_cast<uintptr_t>(kc) & 7) == 0, "ds_pack_kc: kc must be 8-byte aligned");
-    pack_kc_kernel<<<(unsigned)ds::ceil_div(nnzb * 3, 256), 256, 0, ds::as_stream(stream)>>>(k32, kperm, nnzb,
-                                                                                            static_cast<i2s*>(kc));
-    DS_LAUNCH_CHECK("pack_kc_kernel");
-    return DS_OK;
-}
-
-template <int G, int NT, int BATCH, int LVL, int TAIL>
-static int launch_mfma(int epilogue, int y_f32, const int32_t* gptr, const int32_t* gcol, const int32_t* gmeta,
-                       const int32_t* gbase, const int32_t* ghead, const void* kc, int64_t nnzb, int64_t ngroups, int64_t nv, const float* X,
-                       int64_t ldx, float* Y, int64_t ldy, int lpn, int acap, hipStream_t st, const ChebEpilogue& epi) {
-    const char* kcp = static_cast<const char*>(kc);
-    const size_t lds = (size_t)mf_panel_bytes(lpn * 4, G, BATCH, TAIL) + (size_t)acap + 32;
-    if (epilogue == 2)
-        spmm_union_mfma_kernel<G, NT, 2, false, BATCH, LVL, TAIL><<<(unsigned)ngroups, 64, lds, st>>>(gptr, gcol, gmeta, gbase, ghead, kcp, nnzb, (unsigned)ngroups, nv, X, ldx, Y, ldy, lpn, acap, epi);
-    else if (y_f32)
-        spmm_union_mfma_kernel<G, NT, 1, true, BATCH, LVL, TAIL><<<(unsigned)ngroups, 64, lds, st>>>(gptr, gcol, gmeta, gbase, ghead, kcp, nnzb, (unsigned)ngroups, nv, X, ldx, Y, ldy, lpn, acap, epi);
-    else
-        spmm_union_mfma_kernel<G, NT, 1, false, BATCH, LVL, TAIL><<<(unsigned)ngroups, 64, lds, st>>>(gptr, gcol, gmeta, gbase, ghead, kcp, nnzb, (unsigned)ngroups, nv, X, ldx, Y, ldy, lpn, acap, epi);
-    DS_LAUNCH_CHECK("spmm_union_mfma_kernel");
-    return DS_OK;
-}
-
-// entries per batch on the corner-node level (level_tag 1): DS_MF_BATCH, or twice that (one wave's chain of dependent round
-// trips is what a level with about as many groups as the device has wave slots is made of; measured at C3's corner level,
-// 2 461 groups: see profiles/r04_corner_batch_ab.txt)
-#ifndef DS_MF_CORNER_BATCH
-#define DS_MF_CORNER_BATCH DS_MF_BATCH
-#endif
-
-extern "C" int ds_spmm_union16m(int epilogue, int group_nodes, int level_tag, const int32_t* gptr, const int32_t* gcol,
-                                const int32_t* gmeta, const int32_t* gbase, const int32_t* ghead, const void* kc, int64_t nnzb,
-                                int64_t ngroups, int max_entries, int max_batch_blocks, int64_t nv, const void* X,
-                                int64_t ldx, void* Y,
-                                int64_t ldy, int y_f32, const void* R0, int64_t ldr, const float* dinv, int ncols,
-                                float c1, float c2, int first, const void* Wprev, int64_t ldp, ds_stream_t stream) {
-    DS_REQUIRE(gptr && gcol && gmeta && gbase && ghead && kc && X && Y && R0, "ds_spmm_union16m: null pointer");
-    DS_REQUIRE((reinterpret_cast<uintptr_t>(ghead) & 3) == 0 && ngroups * 512 < (int64_t)1 << 40, "ds_spmm_union16m: bad ghead");
-    DS_REQUIRE(epilogue == 1 || epilogue == 2, "ds_spmm_union16m: epilogue must be 1 (Chebyshev term) or 2 (residual)");
-    DS_REQUIRE(epilogue != 1 || dinv, "ds_spmm_union16m: the Chebyshev epilogue needs dinv");
-    // (4-node groups were slower on both levels; only the 8-node kernel is built)
-    DS_REQUIRE(group_nodes == 8, "ds_spmm_union16m: groups of 8 nodes");
-    DS_REQUIRE(level_tag == 0 || level_tag == 1, "ds_spmm_union16m: level_tag must be 0 (fine) or 1 (corner-node level)");
-    DS_REQUIRE(nv > 0 && ngroups == (nv + group_nodes - 1) / group_nodes && ncols > 0 && ncols % 4 == 0 && ncols <= 84,
-               "ds_spmm_union16m: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / group_nodes)");
-    DS_REQUIRE(max_entries > 0 && max_entries <= 256, "ds_spmm_union16m: a group with %d union entries exceeds 256", max_entries);
-    DS_REQUIRE(max_batch_blocks > 0 && max_batch_blocks <= DS_MF_BATCH * group_nodes,
-               "ds_spmm_union16m: max_batch_blocks must be in (0, DS_MF_BATCH x group_nodes]");
-    DS_REQUIRE(nnzb > 0 && nnzb * 24 < (int64_t)PIPE_OOB, "ds_spmm_union16m: the block array exceeds the descriptor range");
-    DS_REQUIRE(ldx >= ncols && ldy >= ncols && ldr >= ncols, "ds_spmm_union16m: leading dimension smaller than ncols");
-    DS_REQUIRE(X != Y, "ds_spmm_union16m: X and Y must be different buffers");
-    DS_REQUIRE(3 * nv * std::max(std::max(ldx, ldr), ldp) * 2 < (int64_t)PIPE_OOB && nv * 36 < (int64_t)PIPE_OOB,
-               "ds_spmm_union16m: a bf16 operand block exceeds the descriptor range");
-    uintptr_t al = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(R0) | (uintptr_t)(ldx * 2) | (uintptr_t)(ldr * 2);
-    al |= reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldy * (y_f32 ? 4 : 2)) | reinterpret_cast<uintptr_t>(kc);
-    DS_REQUIRE((al & 7) == 0 && (!y_f32 || ((reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldy * 4)) & 15) == 0),
-               "ds_spmm_union16m: bf16 rows and kc must be 8-byte aligned (fp32 output rows 16-byte)");
-    DS_REQUIRE(!y_f32 || epilogue == 1, "ds_spmm_union16m: an fp32 result is the Chebyshev term's only");
-    hipStream_t st = ds::as_stream(stream);
-    ChebEpilogue epi{static_cast<const float*>(R0), ldr, dinv, c1, c2, first};
-    if (Wprev && epilogue == 1) {
-        DS_REQUIRE(ldp >= ncols && ((reinterpret_cast<uintptr_t>(Wprev) | (uintptr_t)(ldp * 2)) & 7) == 0 && Wprev != X,
-                   "ds_spmm_union16m: bad W_prev block");
-        epi.wprev = static_cast<const float*>(Wprev), epi.ldp = ldp;
-    }
-    const float* Xf = static_cast<const float*>(X);
-    float* Yf = static_cast<float*>(Y);
-    const int lpn = ncols / 4;
-    const int nt = (ncols + 15) / 16;
-    // two batches of DS_MF_BATCH entries never hold more blocks than 2 x max_batch_blocks
-    constexpr int CB = DS_MF_CORNER_BATCH;
-    const int acap = ((max_batch_blocks * 24 + 1023) / 1024) * 1024;  // whole 1 KiB staging pieces
-    const int acapc = (((CB / DS_MF_BATCH) * max_batch_blocks * 24 + 1023) / 1024) * 1024;
-    // groups of at most 128 entries: the form whose last batch takes DS_MF_TAIL entries more (see spmm_mfma.inc)
-    const bool tail = max_entries <= 128 && max_batch_blocks * 24 <= 2048;
-    constexpr int CT = CB == DS_MF_BATCH ? DS_MF_TAIL : 0;
-#define DS_MF_ARGS(ACAP) epilogue, y_f32, gptr, gcol, gmeta, gbase, ghead, kc, nnzb, ngroups, nv, Xf, ldx, Yf, ldy, lpn, ACAP, st, epi
-    // (blocks of >= 49 columns only: with fewer accumulator tiles the compiler spills the tail form at three waves per SIMD)
-#define DS_MF_GO(N) return tail ? launch_mfma<8, N, DS_MF_BATCH, 0, (N >= 4 ? DS_MF_TAIL : 0)>(DS_MF_ARGS(acap)) : launch_mfma<8, N, DS_MF_BATCH, 0, 0>(DS_MF_ARGS(acap))
-#define DS_MF_GOC(N) return tail ? launch_mfma<8, N, CB, 1, (N >= 4 ? CT : 0)>(DS_MF_ARGS(acapc)) : launch_mfma<8, N, CB, 1, 0>(DS_MF_ARGS(acapc))
-    auto go = [&]() -> int {
-        if (level_tag == 1) {
-            switch (nt) {
-                case 1: DS_MF_GOC(1); case 2: DS_MF_GOC(2); case 3: DS_MF_GOC(3);
-                case 4: DS_MF_GOC(4); case 5: DS_MF_GOC(5); default: DS_MF_GOC(6);
-            }
-        }
-        switch (nt) {
-            case 1: DS_MF_GO(1); case 2: DS_MF_GO(2); case 3: DS_MF_GO(3);
-            case 4: DS_MF_GO(4); case 5: DS_MF_GO(5); default: DS_MF_GO(6);
-        }
-    };
-#undef DS_MF_GO
-#undef DS_MF_GOC
-#undef DS_MF_ARGS
-    ds::ProfScope prof((epilogue == 1 && !y_f32) ? stream : nullptr, DS_PROF_TERM, nv, nnzb, ncols, (first ? 1 : 0) | (2 << 8));
-    return go();
-}
-
-// ------------------------------------------------------------------------------------------------
-// fp32 matrix-core form of the eigensolver's own products (spmm_mfma32.inc)
-#ifndef DS_MF32_BATCH
-#define DS_MF32_BATCH 8
-#endif
-template <int NT, int EPI, int LVL>
-static int launch_mfma32(const int32_t* gptr, const int32_t* gcol, const int32_t* gmeta, const int32_t* gbase, const float* vals,
-                         unsigned vals_bytes, int64_t ngroups, int64_t nv, const float* X, int64_t ldx, float* Y, int64_t ldy,
-                         int lpn, hipStream_t st) {
-    constexpr int EB = DS_MF32_BATCH;
-    constexpr int acap = ((EB * MF32_G * (EPI == 3 ? 4 : 36) + 1023) / 1024) * 1024;  // whole 1 KiB staging pieces
-    const size_t lds = (size_t)mf32_panel_bytes(NT, EB) + acap + 48;
-    spmm_union_mfma32_kernel<NT, EPI, EB, LVL><<<(unsigned)ngroups, 64, lds, st>>>(gptr, gcol, gmeta, gbase, vals, vals_bytes,
-                                                                                  (unsigned)ngroups, nv, X, ldx, Y, ldy, lpn, acap);
-    DS_LAUNCH_CHECK("spmm_union_mfma32_kernel");
-    return DS_OK;
-}
-
-extern "C" int ds_spmm_union32m(int epilogue, int level_tag, const int32_t* gptr, const int32_t* gcol, const int32_t* gmeta,
-                                const int32_t* gbase, const float* vals, int64_t vals_bytes, int64_t nblocks, int64_t ngroups,
-                                int max_entries, int max_batch_blocks, int64_t nv, const float* X, int64_t ldx, float* Y,
-                                int64_t ldy, int ncols, ds_stream_t stream) {
-    DS_REQUIRE(gptr && gcol && gmeta && gbase && vals && X && Y, "ds_spmm_union32m: null pointer");
-    DS_REQUIRE(epilogue == 0 || epilogue == 3, "ds_spmm_union32m: epilogue must be 0 (3x3 blocks) or 3 (node-scalar values)");
-    DS_REQUIRE(level_tag == 0 || level_tag == 1, "ds_spmm_union32m: level_tag must be 0 (fine) or 1 (corner-node level)");
-    DS_REQUIRE(nv > 0 && ngroups == (nv + MF32_G - 1) / MF32_G && ncols > 0 && ncols % 4 == 0 && ncols <= 84,
-               "ds_spmm_union32m: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / 4)");
-    DS_REQUIRE(max_entries > 0 && max_entries <= 256, "ds_spmm_union32m: a group with %d union entries exceeds 256", max_entries);
-    DS_REQUIRE(max_batch_blocks > 0 && max_batch_blocks <= DS_MF32_BATCH * MF32_G,
-               "ds_spmm_union32m: max_batch_blocks must be in (0, DS_MF32_BATCH x 4]");
-    const int64_t vb = epilogue == 3 ? 4 : 36;
-    // (the value stream is read in 16-byte pieces: the array carries 16 bytes of slack behind its last block)
-    DS_REQUIRE(nblocks > 0 && vals_bytes >= nblocks * vb + 16 && vals_bytes < (int64_t)PIPE_OOB,
-               "ds_spmm_union32m: the value array must hold nblocks x %d bytes + 16 of slack, under the descriptor range", (int)vb);
-    DS_REQUIRE(ldx >= ncols && ldy >= ncols, "ds_spmm_union32m: leading dimension smaller than ncols");
-    DS_REQUIRE(X != Y, "ds_spmm_union32m: X and Y must be different buffers");
-    DS_REQUIRE(3 * nv * ldx * 4 < (int64_t)PIPE_OOB, "ds_spmm_union32m: the operand block exceeds the descriptor range");
-    const uintptr_t al = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldx * 4) | (uintptr_t)(ldy * 4);
-    DS_REQUIRE((al & 15) == 0 && (reinterpret_cast<uintptr_t>(vals) & 3) == 0, "ds_spmm_union32m: rows must be 16-byte aligned");
-    hipStream_t st = ds::as_stream(stream);
-    const int lpn = ncols / 4, nt = (ncols + 15) / 16;
-#define DS_M32_GO(N, E, L) return launch_mfma32<N, E, L>(gptr, gcol, gmeta, gbase, vals, (unsigned)vals_bytes, ngroups, nv, X, ldx, Y, ldy, lpn, st)
-#define DS_M32_NT(E, L)                                                                     \
-    switch (nt) {                                                                           \
-        case 1: DS_M32_GO(1, E, L); case 2: DS_M32_GO(2, E, L); case 3: DS_M32_GO(3, E, L); \
-        case 4: DS_M32_GO(4, E, L); case 5: DS_M32_GO(5, E, L); default: DS_M32_GO(6, E, L); \
-    }
-    if (epilogue == 0) {
-        if (level_tag == 0) DS_M32_NT(0, 0)
-        DS_M32_NT(0, 1)
-    }
-    if (level_tag == 0) DS_M32_NT(3, 0)
-    DS_M32_NT(3, 1)
-#undef DS_M32_NT
-#undef DS_M32_GO
-}
-
-#ifdef DS_DIAG
-extern "C" int ds_m32_diag(unsigned long long* out, int nwaves) {  // diagnostic build only: out[nwaves][8]
-    return ds::check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_m32_dbg), (size_t)nwaves * 8 * sizeof(unsigned long long)), "ds_m32_diag read");
-}
-extern "C" int ds_mf_diag(unsigned long long* out, int nwaves) {  // the bf16 term kernel's records
-    return ds::check_hip(hipMemcpyFromSymbol(out, HIP_SYMBOL(g_mf_dbg), (size_t)nwaves * 8 * sizeof(unsigned long long)), "ds_mf_diag read");
-}
-#endif
 
 // fp64 values (and fp64 or fp32 vectors) on the neighbour-union tables (spmm_f64_union.inc): the fp64 refinement's K W / M W
 extern "C" int ds_spmm_f64_union(int kind, int x_f64, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,

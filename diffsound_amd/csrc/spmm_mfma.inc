@@ -1,5 +1,5 @@
-// MFMA form of the preconditioner's bf16 terms.  Included from spmm.hip (inside its anonymous namespace, after
-// spmm_union.inc whose load / wait helpers it uses).
+// MFMA form of the preconditioner's bf16 terms.  Included from spmm_mfma.hip (inside its anonymous namespace, after
+// spmm_device.h whose descriptor and bf16 helpers it uses).
 //
 // The VALU kernel (spmm_union.inc) spends about as long multiplying as gathering: ~40 wave-instructions per union
 // entry (10 packed FMAs, the coefficient reads, the bf16 unpack, the mask walk), ~90 us of vector-unit time per

@@ -1,5 +1,5 @@
 // fp32 matrix-core form of the eigensolver's OWN products: K W (3x3 blocks) and M W / M X (node-scalar mass values) on
-// blocks of <= 84 columns.  Included from spmm.hip (inside its anonymous namespace, after spmm_mfma.inc whose vector
+// blocks of <= 84 columns.  Included from spmm_mfma32.hip (inside its anonymous namespace, after spmm_device.h whose vector
 // types and load helpers it uses).  Replaces torch.sparse.mm(A, X) of the reference's solver
 // (src/lobpcg/_linalg_utils.py:36-37) for the fp32 iterates.
 //

@@ -1,14 +1,5 @@
 // Neighbour-union SpMM (the production kernel of the <= 84-column products on both levels) and its inline-asm load /
-// wait helpers.  Included from spmm.hip inside its anonymous namespace.
-constexpr int PIPE_OOB = 0x7f000000;  // byte offset no block reaches: a load at it is answered with zeros, no request
-// NON-TEMPORAL HINTS on what a wave touches once (round 5; A/B of four builds on one box, profiles/r05_nt_hint_ab.txt): result rows
-// are STORED non-temporal on both levels (K W 182 -> 177 us, M W 149 -> 130, [K W | M W] 228 -> 224, fused residual 241 -> 236: the
-// rows written no longer push the gathered panels, which the neighbouring groups re-use, out of the L2), and the value / table
-// streams are LOADED non-temporal on the FINE level only (bf16 term 117 -> 112 us; with both hints K W 169, M W 129; the
-// corner-node level re-reads its 7 MB of values 21 times per polynomial out of the L2 and loses 4 % with the hint).
-#define DS_STREAM_LOAD(LVL_, p) ((LVL_) == 0 ? __builtin_nontemporal_load(p) : *(p))
-#define DS_STREAM_STORE(p, v) __builtin_nontemporal_store(v, p)
-
+// wait helpers.  Included from spmm.hip inside its anonymous namespace, after spmm_device.h.
 // Phase B issues its loads through inline asm and waits with explicit counted s_waitcnt: left to the
 // compiler, the FMAs sink below the re-issued loads, the window is renamed into fresh registers and copied
 // back behind a vmcnt(0) at the loop latch (seen in the ISA of the first version of this kernel).  The loaded
@@ -18,21 +9,6 @@ constexpr int PIPE_OOB = 0x7f000000;  // byte offset no block reaches: a load at
 // PROVIDED every load of the phase is a buffer_load: global_load_* operand loads mixed into the window were
 // overtaken by younger buffer loads on gfx950 (first nodes of a batch read stale operands; found with
 // tools/dbg_cheb1.py), so the epilogue operands go through descriptors as well.
-using i4s = __attribute__((ext_vector_type(4))) int;
-using f3v = __attribute__((ext_vector_type(3))) float;
-__device__ __forceinline__ i4s make_rsrc_words(const void* p, unsigned bytes) {
-    const uint64_t a = reinterpret_cast<uint64_t>(p);
-    i4s r;
-    r.x = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
-    r.y = __builtin_amdgcn_readfirstlane((int)((unsigned)(a >> 32) & 0xffffu));  // stride 0
-    r.z = __builtin_amdgcn_readfirstlane((int)bytes);
-    r.w = 0x00020000;
-    // The words were written by v_readfirstlane (VALU -> SGPR); a VMEM instruction must not read such an SGPR within
-    // 5 wait states, and the compiler cannot pad inline-asm loads.  Passing the words through this asm pins the
-    // readfirstlanes BEFORE it (they cannot be re-materialised next to a later use) and pays the wait states once.
-    asm volatile("s_nop 4" : "+s"(r));
-    return r;
-}
 // descriptor of panel `idx` (wave-uniform) of a block whose descriptor words are `base`: base address + idx * bytes
 __device__ __forceinline__ i4s rebase_rsrc(i4s base, int idx, int bytes) {
     const uint64_t a = ((uint64_t)(unsigned)base.x | ((uint64_t)(unsigned)(base.y & 0xffff) << 32)) +
@@ -42,23 +18,6 @@ __device__ __forceinline__ i4s rebase_rsrc(i4s base, int idx, int bytes) {
     r.y = (int)((unsigned)(a >> 32) & 0xffffu);
     asm volatile("s_nop 4" : "+s"(r));  // (should the compiler route the arithmetic through the vector unit)
     return r;
-}
-// bf16 storage of the preconditioner's iterates (the V-cycle is insensitive to 8-bit mantissas - same outer iteration
-// counts - and its fused terms are bound by the bytes of the four vector streams): two bf16 per dword, fp32 arithmetic
-using i2s = __attribute__((ext_vector_type(2))) int;
-__device__ __forceinline__ f4v unpack_bf16x4(i2s w) {
-    f4v r;
-    r.x = __builtin_bit_cast(float, w.x << 16);
-    r.y = __builtin_bit_cast(float, w.x & (int)0xffff0000);
-    r.z = __builtin_bit_cast(float, w.y << 16);
-    r.w = __builtin_bit_cast(float, w.y & (int)0xffff0000);
-    return r;
-}
-__device__ __forceinline__ i2s pack_bf16x4(f4v v) {  // round to nearest even (v_cvt_pk_bf16_f32)
-    using bf2 = __attribute__((ext_vector_type(2))) __bf16;
-    using f2_ = __attribute__((ext_vector_type(2))) float;
-    const bf2 lo = __builtin_convertvector(f2_{v.x, v.y}, bf2), hi = __builtin_convertvector(f2_{v.z, v.w}, bf2);
-    return i2s{__builtin_bit_cast(int, lo), __builtin_bit_cast(int, hi)};
 }
 #define DS_BUF_LOAD4(dst, voff, rsrc, soff) \
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "+v"(dst) : "v"(voff), "s"(rsrc), "s"(soff) : "memory")

@@ -372,7 +372,7 @@ int ds_spmm_union16(int epilogue, const int32_t* utab, const int32_t* ctab, int6
                     const int32_t* gent, const float* kgrp, int64_t nnzb, int64_t nv, const void* X, int64_t ldx,
                     void* Y, int64_t ldy, int y_f32, const void* R0, int64_t ldr, const float* dinv, int ncols,
                     float c1, float c2, int first, const void* Wprev, int64_t ldp, ds_stream_t stream);
-/* MFMA form of ds_spmm_union16 (csrc/spmm_mfma.inc): the same two epilogues on the same bf16 blocks, the block
+/* MFMA form of ds_spmm_union16 (csrc/spmm_mfma.hip, kernels in spmm_mfma.inc): the same two epilogues on the same bf16 blocks, the block
  * products on the matrix cores (v_mfma_f32_16x16x16_bf16; the 3x3 blocks rounded to bf16, fp32 accumulation), one
  * wavefront per group of group_nodes = 8 consecutive nodes.  Topology tables (device): gptr (ngroups + 1) / gcol =
  * the sorted union of the column ids of each group's rows; gmeta per entry = presence mask of the group's nodes |
@@ -408,7 +408,7 @@ int ds_spmm_union16m(int epilogue, int group_nodes, int level_tag, const int32_t
                      const void* R0, int64_t ldr,
                      const float* dinv, int ncols, float c1, float c2, int first, const void* Wprev, int64_t ldp,
                      ds_stream_t stream);
-/* fp32 matrix-core form of ds_spmm_union epilogues 0 and 3 (csrc/spmm_mfma32.inc) - the eigensolver's own products
+/* fp32 matrix-core form of ds_spmm_union epilogues 0 and 3 (csrc/spmm_mfma32.hip, kernel in spmm_mfma32.inc) - the eigensolver's own products
  * K W, M W, M X on fp32 blocks of <= 84 columns (reference: torch.sparse.mm in src/lobpcg/_linalg_utils.py:36-37):
  * one wavefront per group of 4 consecutive nodes, the gathered panels of a batch of DS_MF32_BATCH union entries staged
  * in LDS as the B operand of v_mfma_f32_16x16x4_f32 (exact fp32: one rounding per product), the 3x3 blocks (epilogue 0:

@@ -96,25 +96,8 @@ def test_no_cpu_fallback():
         DiffSoundObj(vertices=v, tets=t, mode_num=2)
 
 
-def _gfx950_code_objects(lib_path):
-    """The gfx950 code objects inside a HIP shared library: the .hip_fatbin section is a sequence of clang offload
-    bundles (one per translation unit: magic, entry count, then (offset, size, triple) records)."""
-    import struct
-
-    data = open(lib_path, "rb").read()
-    magic = b"__CLANG_OFFLOAD_BUNDLE__"
-    pos, out = data.find(magic), []
-    while pos >= 0:
-        (n,) = struct.unpack_from("<Q", data, pos + len(magic))
-        p = pos + len(magic) + 8
-        for _ in range(n):
-            off, size, tlen = struct.unpack_from("<QQQ", data, p)
-            triple = data[p + 24:p + 24 + tlen].decode()
-            p += 24 + tlen
-            if "gfx950" in triple and size:
-                out.append(data[pos + off:pos + off + size])
-        pos = data.find(magic, pos + len(magic))
-    return out
+# (the parser of the library's offload bundles is shared with tools/kernel_digest.py)
+from tools.kernel_digest import gfx950_code_objects as _gfx950_code_objects  # noqa: E402
 
 
 def test_library_issues_no_packed_fp32_and_no_double_rate_bf16_mfma(tmp_path):
