@@ -1,7 +1,7 @@
 // bf16-storage pieces of the two-level preconditioner - gfx950.  The V-cycle (csrc/vcycle.cpp) keeps its iterates,
 // residuals and corner-level blocks in bf16 (fp32 arithmetic in registers): the outer iteration count of the
 // eigensolver does not notice an 8-bit mantissa in its PRECONDITIONER, and every term of the cycle is bound by the
-// bytes of its vector streams.  The fused SpMM terms are ds_spmm_union16 (spmm.hip); here are the two streaming steps:
+// bytes of its vector streams.  The fused SpMM terms are ds_spmm_union16 (spmm_union.hip); here are the two streaming steps:
 //   ds_cheb_init16        W1 = c T R (block-Jacobi, first Chebyshev iterate) written as bf16 - R fp32 (the solver's
 //                         residual block: a bf16 copy of it is written alongside, every later term reads that) or bf16
 //                         (corner level);

@@ -12,12 +12,12 @@
 // address (hardware broadcast).  Accumulation in registers, one store per output element.
 // Algorithmic bytes per launch: nnzb*(vals + 4) + (nv+1)*4 + 2*3nv*ncols*sizeof(T).
 //
-// This unit: the row-wise kernels, the fp64 kernels and the neighbour-union walk with its narrow and fp64 forms (spmm_union.inc,
-// spmm_narrow.inc, spmm_f64_union.inc, included below in this order, after spmm_device.h).  The matrix-core forms are units of
-// their own (spmm_mfma.hip, spmm_mfma32.hip), the launch timing hook is profile.cpp.
-#include <algorithm>
-#include <cstdlib>
-#include <type_traits>
+// This unit: the row-wise family - the generic lane-per-columns kernel (spmm_bsr3_kernel), the wave-per-node fast path of the
+// fp32 products with its fused Chebyshev / residual epilogues (spmm_wave_node_kernel) and the wave-per-node fp64-value kernel
+// that ds_spmm_bsr3 dispatches to (spmm_f64_node_kernel).  Exports ds_spmm_bsr3, ds_cheb_spmm, ds_spmm_residual.  The other
+// families are units of their own: the neighbour-union walk (spmm_union.hip), the read-out's and the refinement's fp64-value
+// products (spmm_f64.hip), the matrix-core forms (spmm_mfma.hip, spmm_mfma32.hip); the launch timing hook is profile.cpp.
+#include <cstdint>
 
 #include "spmm_device.h"
 
@@ -353,10 +353,6 @@ int launch_wn(const int32_t* rowptr, const int32_t* colidx, const void* vals, co
     return DS_OK;
 }
 
-#include "spmm_union.inc"
-#include "spmm_narrow.inc"
-#include "spmm_f64_union.inc"
-
 template <int KIND>
 int launch_fast(const int32_t* rowptr, const int32_t* colidx, const void* vals, const void* vals_t, int64_t nv,
                 const void* X, int64_t ldx, void* Y, int64_t ldy, int ncols, hipStream_t st) {
@@ -384,7 +380,7 @@ int launch_fast(const int32_t* rowptr, const int32_t* colidx, const void* vals, 
 // of every block itself: 12 dependent-address loads per block and lane, 1.17 ms per 64-column product on the
 // benchmark mesh; this one issues 4.
 // (round 4: the row's fp64 coefficients are staged per chunk in LDS with coalesced loads and the neighbour ids come back with
-// v_readlane, as in spmm_f64_polish_kernel below - three dependent-address global loads per block and lane fewer; same sums in
+// v_readlane, as in spmm_f64_polish_kernel (spmm_f64.hip) - three dependent-address global loads per block and lane fewer; same sums in
 // the same order)
 constexpr int F64_CHUNK = 32;  // blocks of a row staged per pass
 constexpr int F64_WIN = 8;     // neighbour panels in flight per wave
@@ -497,154 +493,6 @@ __global__ void __launch_bounds__(256)
     }
 }
 
-// The read-out's three fp64-value products in ONE walk of the pattern: Ya = A X, Yb = B X (3x3 fp64 blocks: K_lambda and
-// K_mu) and Ym = (m (x) I3) X (the node-scalar mass values) share every gathered panel of the fp32 block X.  Three
-// launches of spmm_f64_node_kernel are bound by exactly those gathers (3.2 GB out of L2 per 64-column product at the
-// benchmark size: 0.63 + 0.63 + 0.22 ms); per output the arithmetic and its order are theirs, so the results are
-// bit-identical.
-// Round 4: the row's fp64 coefficients (9 + 9 + 1 doubles per block) no longer come through seven dependent-address global
-// loads per block and lane (the kernel was bound by vector-memory ISSUE: 33 M wave-loads for 4.1 M blocks) but are staged per
-// chunk of the row in LDS with coalesced 8-byte loads and read back as broadcasts; the neighbour ids of the chunk sit in one
-// register (a coalesced load) and come back with v_readlane, so a panel's address is scalar arithmetic.  The sums and their
-// order are unchanged: results bit-identical to the three separate launches, as before.
-constexpr int PL_CHUNK = 32;  // blocks of a row staged per pass
-constexpr int PL_WIN = 4;     // panels per gather window (two windows: 8 in flight)
-// TY: the type the three results are STORED in - double, or float (round 5: the sums are formed in fp64 either way and rounded
-// once; the fp32 blocks halve the 0.86 GB the kernel writes and the Gram launch behind it reads, and that Gram then runs on the
-// fp32 matrix-core path; a result entry carries 6e-8 of relative rounding, the Gram entries ~1e-10 - see polish_products)
-template <typename TY>
-__global__ void __launch_bounds__(256)
-    spmm_f64_polish_kernel(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
-                           const double* __restrict__ va, const double* __restrict__ vb, const double* __restrict__ vm,
-                           int64_t nv, const float* __restrict__ X, int64_t ldx, TY* __restrict__ Ya,
-                           TY* __restrict__ Yb, TY* __restrict__ Ym, int64_t ldy, int lpn, unsigned nblk) {
-    using d2 = __attribute__((ext_vector_type(2))) double;
-    using xv4 = __attribute__((ext_vector_type(4))) float;
-    __shared__ double s_a[4][PL_CHUNK * 9], s_b[4][PL_CHUNK * 9], s_m[4][PL_CHUNK];
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int64_t node = (int64_t)ds::xcd_remap(blockIdx.x, nblk) * 4 + wave;
-    if (node >= nv) return;  // wave-uniform
-    const int g = lane / lpn, cl = lane - g * lpn;
-    const bool active = g < 3;
-    const int ga = active ? g : 0;
-    const int kb = __builtin_amdgcn_readfirstlane(rowptr[node]), ke = __builtin_amdgcn_readfirstlane(rowptr[node + 1]);
-    const float* xb = X + (int64_t)ga * ldx + cl * 4;
-    double* sa = s_a[wave];
-    double* sb = s_b[wave];
-    double* sm = s_m[wave];
-    double aa[3][4], ab[3][4], am[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        am[v] = 0.0;
-#pragma unroll
-        for (int r = 0; r < 3; ++r) aa[r][v] = ab[r][v] = 0.0;
-    }
-    for (int kc = kb; kc < ke; kc += PL_CHUNK) {
-        const int cnt = min(PL_CHUNK, ke - kc);  // wave-uniform
-        const int colreg = colidx[kc + min(lane, cnt - 1)];
-        const double* pa = va + (int64_t)kc * 9;
-        const double* pb = vb + (int64_t)kc * 9;
-        {  // all the chunk's coefficient loads in flight at once (clamped, not predicated)
-            constexpr int NSL = (PL_CHUNK * 9 + 63) / 64;
-            double ra[NSL], rb[NSL];
-#pragma unroll
-            for (int i = 0; i < NSL; ++i) {
-                const int t = min(lane + 64 * i, cnt * 9 - 1);
-                ra[i] = __builtin_nontemporal_load(pa + t), rb[i] = __builtin_nontemporal_load(pb + t);  // (read once)
-            }
-            const double rm = vm[kc + min(lane, cnt - 1)];
-#pragma unroll
-            for (int i = 0; i < NSL; ++i)
-                if (lane + 64 * i < cnt * 9) sa[lane + 64 * i] = ra[i], sb[lane + 64 * i] = rb[i];
-            if (lane < cnt) sm[lane] = rm;
-        }
-        // same-wave LDS write -> read (rows differ in length: no workgroup barrier)
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        // Two windows of PL_WIN panel gathers: the next window is requested before the current one is used (see
-        // spmm_f64_node_kernel); same sums, same order
-        auto issue = [&](xv4 (&xs)[PL_WIN], int u0) {
-#pragma unroll
-            for (int j = 0; j < PL_WIN; ++j) {
-                const int64_t col = __builtin_amdgcn_readlane(colreg, min(u0 + j, cnt - 1));
-                xs[j] = *reinterpret_cast<const xv4*>(xb + col * 3 * ldx);
-            }
-        };
-        auto consume = [&](const xv4 (&xs)[PL_WIN], int u0) {
-#pragma unroll
-            for (int j = 0; j < PL_WIN; ++j) {
-                if (u0 + j < cnt) {  // wave-uniform
-                    const int u = u0 + j;
-                    const double* ca = sa + u * 9 + ga;  // column g of the blocks
-                    const double* cb = sb + u * 9 + ga;
-                    const double a0 = ca[0], a1 = ca[3], a2 = ca[6], b0 = cb[0], b1 = cb[3], b2 = cb[6], m = sm[u];
-#pragma unroll
-                    for (int v = 0; v < 4; ++v) {
-                        const double xv = (double)xs[j][v];
-                        aa[0][v] = fma(a0, xv, aa[0][v]);
-                        aa[1][v] = fma(a1, xv, aa[1][v]);
-                        aa[2][v] = fma(a2, xv, aa[2][v]);
-                        ab[0][v] = fma(b0, xv, ab[0][v]);
-                        ab[1][v] = fma(b1, xv, ab[1][v]);
-                        ab[2][v] = fma(b2, xv, ab[2][v]);
-                        am[v] = fma(m, xv, am[v]);
-                    }
-                }
-            }
-        };
-        xv4 x0[PL_WIN], x1[PL_WIN];
-        issue(x0, 0);
-        for (int u0 = 0; u0 < cnt; u0 += 2 * PL_WIN) {
-            issue(x1, u0 + PL_WIN);  // (a window past the chunk re-reads its last panel and is skipped)
-            consume(x0, u0);
-            issue(x0, u0 + 2 * PL_WIN);
-            consume(x1, u0 + PL_WIN);
-        }
-        if (kc + PL_CHUNK < ke) {  // the slabs are rewritten by the next pass
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
-    // lane (g, cl) ends with output row g: its own share plus the shares of the two other groups (as the node kernel)
-    double oa[4], ob[4];
-#pragma unroll
-    for (int v = 0; v < 4; ++v) {
-        oa[v] = ga == 0 ? aa[0][v] : (ga == 1 ? aa[1][v] : aa[2][v]);
-        ob[v] = ga == 0 ? ab[0][v] : (ga == 1 ? ab[1][v] : ab[2][v]);
-    }
-#pragma unroll
-    for (int s_ = 1; s_ <= 2; ++s_) {
-        const int to_row = (ga + s_) % 3;
-        int src_g = ga - s_;
-        if (src_g < 0) src_g += 3;
-        const int src_lane = active ? src_g * lpn + cl : lane;
-#pragma unroll
-        for (int v = 0; v < 4; ++v) {
-            const double sa = to_row == 0 ? aa[0][v] : (to_row == 1 ? aa[1][v] : aa[2][v]);
-            const double sb = to_row == 0 ? ab[0][v] : (to_row == 1 ? ab[1][v] : ab[2][v]);
-            oa[v] += __shfl(sa, src_lane, 64);
-            ob[v] += __shfl(sb, src_lane, 64);
-        }
-    }
-    if (active) {
-        const int64_t o = (node * 3 + g) * ldy + cl * 4;
-        if constexpr (sizeof(TY) == 8) {
-            __builtin_nontemporal_store(d2{oa[0], oa[1]}, reinterpret_cast<d2*>(Ya + o));  // (written once)
-            __builtin_nontemporal_store(d2{oa[2], oa[3]}, reinterpret_cast<d2*>(Ya + o + 2));
-            __builtin_nontemporal_store(d2{ob[0], ob[1]}, reinterpret_cast<d2*>(Yb + o));
-            __builtin_nontemporal_store(d2{ob[2], ob[3]}, reinterpret_cast<d2*>(Yb + o + 2));
-            __builtin_nontemporal_store(d2{am[0], am[1]}, reinterpret_cast<d2*>(Ym + o));
-            __builtin_nontemporal_store(d2{am[2], am[3]}, reinterpret_cast<d2*>(Ym + o + 2));
-        } else {
-            *reinterpret_cast<xv4*>(Ya + o) = xv4{(float)oa[0], (float)oa[1], (float)oa[2], (float)oa[3]};
-            *reinterpret_cast<xv4*>(Yb + o) = xv4{(float)ob[0], (float)ob[1], (float)ob[2], (float)ob[3]};
-            *reinterpret_cast<xv4*>(Ym + o) = xv4{(float)am[0], (float)am[1], (float)am[2], (float)am[3]};
-        }
-    }
-}
-
 }  // namespace
 
 extern "C" int ds_spmm_bsr3(int kind, const int32_t* rowptr, const int32_t* colidx, const void* vals,
@@ -702,25 +550,6 @@ extern "C" int ds_spmm_bsr3(int kind, const int32_t* rowptr, const int32_t* coli
                      : launch<1, double, float, double, 2>(rowptr, colidx, vals, nv, X, ldx, Y, ldy, ncols, st);
 }
 
-// ------------------------------------------------------------------------------------------------
-// Pack the (transposed) blocks into the entry-major / node-minor order of the neighbour-union tables.
-__global__ void pack_groups_kernel(const float* __restrict__ vals_t, const int32_t* __restrict__ kperm, int64_t nnzb,
-                                   float* __restrict__ kgrp) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nnzb * 9) return;
-    const int64_t p = i / 9;
-    kgrp[i] = vals_t[(int64_t)kperm[p] * 9 + (i - p * 9)];
-}
-
-extern "C" int ds_pack_groups(const float* vals_t, const int32_t* kperm, int64_t nnzb, float* kgrp,
-                              ds_stream_t stream) {
-    DS_REQUIRE(vals_t && kperm && kgrp && nnzb > 0, "ds_pack_groups: bad argument");
-    pack_groups_kernel<<<(unsigned)ds::ceil_div(nnzb * 9, 256), 256, 0, ds::as_stream(stream)>>>(vals_t, kperm, nnzb,
-                                                                                                kgrp);
-    DS_LAUNCH_CHECK("pack_groups_kernel");
-    return DS_OK;
-}
-
 extern "C" int ds_cheb_spmm(const int32_t* rowptr, const int32_t* colidx, const float* vals, int64_t nv, const float* W,
                             int64_t ldw, float* Wprev, int64_t ldp, const float* R0, int64_t ldr, const float* dinv,
                             int ncols, float c1, float c2, int first, ds_stream_t stream) {
@@ -762,335 +591,4 @@ extern "C" int ds_spmm_residual(const int32_t* rowptr, const int32_t* colidx, co
         case 20: return launch_wn<0, 3, 20, 2>(rowptr, colidx, vals, nullptr, nv, X, ldx, Y, ldy, lpn, st, epi);
         default: return launch_wn<0, 3, 0, 2>(rowptr, colidx, vals, nullptr, nv, X, ldx, Y, ldy, lpn, st, epi);
     }
-}
-
-
-
-extern "C" int ds_spmm_union(int epilogue, int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
-                             const int32_t* gent,
-                             const float* kgrp, int64_t nnzb, int64_t nv, const float* X, int64_t ldx, float* Y,
-                             int64_t ldy, const float* R0, int64_t ldr, const float* dinv, int ncols, float c1, float c2,
-                             int first, const float* Wprev, int64_t ldp, ds_stream_t stream) {
-    DS_REQUIRE(ctab && gent && kgrp && X && Y, "ds_spmm_union: null pointer");
-    DS_REQUIRE(epilogue >= 0 && epilogue <= 3, "ds_spmm_union: bad epilogue %d", epilogue);
-    DS_REQUIRE(level_tag == 0 || level_tag == 1, "ds_spmm_union: level_tag must be 0 (fine) or 1 (corner-node level)");
-    DS_REQUIRE(epilogue == 0 || epilogue == 3 || R0, "ds_spmm_union: the epilogue needs R0");
-    DS_REQUIRE(epilogue != 1 || dinv, "ds_spmm_union: the Chebyshev epilogue needs dinv");
-    DS_REQUIRE(nv > 0 && ngroups == (nv + 3) / 4 && nnzb > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 84,
-               "ds_spmm_union: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / 4)");
-    DS_REQUIRE(cap_blocks > 0 && cap_blocks <= UN_CAPB, "ds_spmm_union: a chunk of %d blocks exceeds the LDS image (DS_UNION_CAP = 140)", cap_blocks);
-    DS_REQUIRE(ldx >= ncols && ldy >= ncols && (epilogue == 0 || epilogue == 3 || ldr >= ncols),
-               "ds_spmm_union: leading dimension smaller than ncols");
-    DS_REQUIRE(X != Y, "ds_spmm_union: X and Y must be different buffers");
-    DS_REQUIRE(ldx * 12 < (int64_t)PIPE_OOB && ldy * 12 < (int64_t)PIPE_OOB && ldr * 12 < (int64_t)PIPE_OOB &&
-                   nv * 36 < (int64_t)PIPE_OOB,
-               "ds_spmm_union: a 3-row panel of %lld bytes exceeds the descriptor range", (long long)(ldx * 12));
-    DS_REQUIRE(nnzb * 36 < ((int64_t)1 << 32), "ds_spmm_union: value array exceeds the descriptor range");
-    uintptr_t al = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldx * 4) |
-                   (uintptr_t)(ldy * 4) | reinterpret_cast<uintptr_t>(kgrp) | reinterpret_cast<uintptr_t>(ctab);
-    if (epilogue == 1 || epilogue == 2) al |= reinterpret_cast<uintptr_t>(R0) | (uintptr_t)(ldr * 4);
-    DS_REQUIRE((al & 15) == 0, "ds_spmm_union: rows, kgrp and ctab must be 16-byte aligned");
-    hipStream_t st = ds::as_stream(stream);
-    ChebEpilogue epi{R0, ldr, dinv, c1, c2, first};
-    if (Wprev && epilogue == 1) {
-        DS_REQUIRE(ldp >= ncols && ldp * 12 < (int64_t)PIPE_OOB &&
-                       ((reinterpret_cast<uintptr_t>(Wprev) | (uintptr_t)(ldp * 4)) & 15) == 0 && Wprev != X,
-                   "ds_spmm_union: bad W_prev block");
-        epi.wprev = Wprev, epi.ldp = ldp;
-    }
-    const int lpn = ncols / 4;
-    // (kinds of the timing hook: the fused term, Y = K X, Y = M_s X; the residual epilogue 2 is not recorded)
-    const int pkind = epilogue == 1 ? DS_PROF_TERM : (epilogue == 0 ? DS_PROF_KX : (epilogue == 3 ? DS_PROF_MX : -1));
-    ds::ProfScope prof(pkind < 0 ? nullptr : stream, pkind < 0 ? 0 : pkind, nv, nnzb, ncols, (first ? 1 : 0) | (4 << 8));
-#define DS_U(L, E) return launch_union<L, E>(utab, ctab, ngroups, cap_blocks, gent, kgrp, nnzb, nv, X, ldx, Y, ldy, lpn, st, epi)
-#define DS_UL(L, E) do { if (level_tag == 1) return launch_union<L, E, false, true, 1>(utab, ctab, ngroups, cap_blocks, gent, kgrp, nnzb, nv, X, ldx, Y, ldy, lpn, st, epi); \
-                         return launch_union<L, E, false, true, 0>(utab, ctab, ngroups, cap_blocks, gent, kgrp, nnzb, nv, X, ldx, Y, ldy, lpn, st, epi); } while (0)
-    if (lpn == 20) {
-        if (epilogue == 1) DS_U(20, 1);
-        if (epilogue == 2) DS_U(20, 2);
-        if (epilogue == 3) DS_UL(20, 3);
-        DS_UL(20, 0);
-    }
-    if (epilogue == 1) DS_U(0, 1);
-    if (epilogue == 2) DS_U(0, 2);
-    if (epilogue == 3) DS_UL(0, 3);
-    DS_UL(0, 0);
-#undef DS_UL
-#undef DS_U
-}
-
-
-// Narrow blocks (<= 16 columns): the lanes dealt over the union's entries (spmm_narrow.inc)
-extern "C" int ds_spmm_union_narrow(int kind, int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups,
-                                    const int32_t* gent, const float* vals, int64_t nnzb, int64_t nv, const float* X, int64_t ldx,
-                                    float* Y, int64_t ldy, int ncols, ds_stream_t stream) {
-    DS_REQUIRE(ctab && gent && vals && X && Y, "ds_spmm_union_narrow: null pointer");
-    DS_REQUIRE(kind == 0 || kind == 3, "ds_spmm_union_narrow: kind must be 0 (3x3 blocks) or 3 (node-scalar values)");
-    DS_REQUIRE(level_tag == 0 || level_tag == 1, "ds_spmm_union_narrow: level_tag must be 0 (fine) or 1 (corner-node level)");
-    DS_REQUIRE(nv > 0 && ngroups == (nv + 3) / 4 && nnzb > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 16,
-               "ds_spmm_union_narrow: ncols must be a multiple of 4 <= 16 and ngroups = ceil(nv / 4)");
-    DS_REQUIRE(ldx >= ncols && ldy >= ncols, "ds_spmm_union_narrow: leading dimension smaller than ncols");
-    DS_REQUIRE(X != Y, "ds_spmm_union_narrow: X and Y must be different buffers");
-    const uintptr_t al = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldx * 4) | (uintptr_t)(ldy * 4) |
-                         reinterpret_cast<uintptr_t>(ctab);
-    DS_REQUIRE((al & 15) == 0, "ds_spmm_union_narrow: rows and ctab must be 16-byte aligned");
-    hipStream_t st = ds::as_stream(stream);
-    const unsigned nwg = (unsigned)ds::ceil_div(ngroups, 4);
-    ds::ProfScope prof(stream, kind == 0 ? DS_PROF_KX : DS_PROF_MX, nv, nnzb, ncols, 4 << 8);
-#define DS_UN(S, V) spmm_union_narrow_kernel<S, V><<<nwg, 256, 0, st>>>(reinterpret_cast<const int2*>(utab), reinterpret_cast<const int4*>(ctab), \
-                                                                       (unsigned)ngroups, gent, vals, nv, X, ldx, Y, ldy, ncols, nwg)
-    if (kind == 0) {
-        if (level_tag == 1) DS_UN(false, 1);
-        else DS_UN(false, 0);
-    } else {
-        if (level_tag == 1) DS_UN(true, 1);
-        else DS_UN(true, 0);
-    }
-#undef DS_UN
-    DS_LAUNCH_CHECK("spmm_union_narrow_kernel");
-    return DS_OK;
-}
-
-// The eigensolver's residual in ONE walk of the unions (spmm_union.inc, epilogue 4): R = K X - (M_s (x) I3) X diag(lam) and
-// the column norms ||R_j||^2, ||X_j||^2, with neither K X nor M X written to memory.
-extern "C" int64_t ds_union_residual_workspace_bytes(int64_t ngroups, int ncols) {
-    return ngroups * 2 * (int64_t)ncols * 4 + (int64_t)UN_NORM_BLOCKS * 2 * ncols * 8;
-}
-
-// (R16 == nullptr: epilogue 4, the fp32 rows of R; else epilogue 6, the bf16 cycle's inputs R16 and W1 in their place)
-static int union_residual(const char* who, int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
-                          const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv, const float* X,
-                          int64_t ldx, const double* lam, float* R, int64_t ldr, const float* dinv, float c, void* R16,
-                          int64_t ldr16, void* W1, int64_t ldw1, int ncols, void* work, int64_t work_bytes, double* rn2,
-                          double* xn2, ds_stream_t stream) {
-    const bool pre = R16 != nullptr;
-    DS_REQUIRE(ctab && gent && kgrp && mgrp && X && lam && (pre ? (W1 && dinv) : R != nullptr) && work && rn2 && xn2, "%s: null pointer", who);
-    DS_REQUIRE(level_tag == 0 || (level_tag == 1 && !pre), "%s: level_tag must be 0 (fine)%s", who, pre ? "" : " or 1 (corner-node level)");
-    DS_REQUIRE(nv > 0 && ngroups == (nv + 3) / 4 && nnzb > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 84,
-               "%s: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / 4)", who);
-    DS_REQUIRE(cap_blocks > 0 && cap_blocks <= UN_CAPB, "%s: a chunk of %d blocks exceeds the LDS image", who, cap_blocks);
-    uintptr_t al = reinterpret_cast<uintptr_t>(X) | (uintptr_t)(ldx * 4) | reinterpret_cast<uintptr_t>(kgrp) |
-                   reinterpret_cast<uintptr_t>(ctab) | reinterpret_cast<uintptr_t>(work);
-    if (pre) {
-        DS_REQUIRE(ldx >= ncols && ldr16 >= ncols && ldw1 >= ncols, "%s: leading dimension smaller than ncols", who);
-        DS_REQUIRE(R16 != W1 && R16 != X && W1 != X, "%s: X, R16 and W1 must be different buffers", who);
-        DS_REQUIRE(ldx * 12 < (int64_t)PIPE_OOB && nv * 36 < (int64_t)PIPE_OOB && nnzb * 36 < ((int64_t)1 << 32),
-                   "%s: operand beyond the descriptor range", who);
-        const uintptr_t al8 = reinterpret_cast<uintptr_t>(R16) | reinterpret_cast<uintptr_t>(W1) | (uintptr_t)(ldr16 * 2) | (uintptr_t)(ldw1 * 2);
-        DS_REQUIRE((al8 & 7) == 0 && (reinterpret_cast<uintptr_t>(dinv) & 3) == 0, "%s: bf16 rows must be 8-byte aligned", who);
-    } else {
-        DS_REQUIRE(ldx >= ncols && ldr >= ncols, "%s: leading dimension smaller than ncols", who);
-        DS_REQUIRE(X != R, "%s: X and R must be different buffers", who);
-        DS_REQUIRE(ldx * 12 < (int64_t)PIPE_OOB && ldr * 12 < (int64_t)PIPE_OOB && nnzb * 36 < ((int64_t)1 << 32),
-                   "%s: operand beyond the descriptor range", who);
-        al |= reinterpret_cast<uintptr_t>(R) | (uintptr_t)(ldr * 4);
-    }
-    DS_REQUIRE((al & 15) == 0, "%s: rows, kgrp, ctab and the workspace must be 16-byte aligned", who);
-    DS_REQUIRE(work_bytes >= ds_union_residual_workspace_bytes(ngroups, ncols), "%s: workspace of %lld bytes needed", who,
-               (long long)ds_union_residual_workspace_bytes(ngroups, ncols));
-    hipStream_t st = ds::as_stream(stream);
-    ChebEpilogue epi{nullptr, 0, pre ? dinv : nullptr, 0.f, pre ? c : 0.f, 0};
-    epi.mvals = mgrp, epi.lam = lam, epi.nwork = static_cast<float*>(work);
-    epi.w1 = W1, epi.ldw1 = ldw1;
-    float* Y = pre ? static_cast<float*>(R16) : R;  // (epilogue 6: bf16 rows, leading dimension in elements)
-    const int64_t ldy = pre ? ldr16 : ldr;
-    const int lpn = ncols / 4;
-    int rc;
-    {
-    ds::ProfScope prof(stream, DS_PROF_RESID, nv, nnzb, ncols, 4 << 8);  // (the walk of the unions; the two norm reductions follow)
-#define DS_UR(L, E, V) rc = launch_union<L, E, false, true, V>(utab, ctab, ngroups, cap_blocks, gent, kgrp, nnzb, nv, X, ldx, Y, ldy, lpn, st, epi)
-    if (lpn == 20) {
-        if (pre) DS_UR(20, 6, 0);
-        else if (level_tag == 1) DS_UR(20, 4, 1);
-        else DS_UR(20, 4, 0);
-    } else {
-        if (pre) DS_UR(0, 6, 0);
-        else if (level_tag == 1) DS_UR(0, 4, 1);
-        else DS_UR(0, 4, 0);
-    }
-#undef DS_UR
-    }
-    if (rc != DS_OK) return rc;
-    double* partial = reinterpret_cast<double*>(static_cast<char*>(work) + ngroups * 2 * (int64_t)ncols * 4);
-    union_norm_partial_kernel<<<UN_NORM_BLOCKS, 256, 0, st>>>(static_cast<const float*>(work), (unsigned)ngroups, 2 * ncols, partial);
-    DS_LAUNCH_CHECK("union_norm_partial_kernel");
-    union_norm_final_kernel<<<(unsigned)(2 * ncols), 256, 0, st>>>(partial, ncols, rn2, xn2);
-    DS_LAUNCH_CHECK("union_norm_final_kernel");
-    return DS_OK;
-}
-
-extern "C" int ds_union_residual(int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
-                                 const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv,
-                                 const float* X, int64_t ldx, const double* lam, float* R, int64_t ldr, int ncols, void* work,
-                                 int64_t work_bytes, double* rn2, double* xn2, ds_stream_t stream) {
-    return union_residual("ds_union_residual", level_tag, utab, ctab, ngroups, cap_blocks, gent, kgrp, mgrp, nnzb, nv, X, ldx, lam, R,
-                          ldr, nullptr, 0.f, nullptr, 0, nullptr, 0, ncols, work, work_bytes, rn2, xn2, stream);
-}
-
-// The same walk for an iteration preconditioned by the bf16 two-level cycle (spmm_union.inc, epilogue 6): instead of the fp32
-// R it writes the cycle's inputs - the bf16 copy R16 and the first Chebyshev iterate W1 = c T R - so that ds_twolevel_apply
-// (DS_TL_PREPARED) starts at its first term.
-extern "C" int ds_union_residual_pre(int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
-                                     const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv,
-                                     const float* X, int64_t ldx, const double* lam, const float* dinv, float c, void* R16,
-                                     int64_t ldr16, void* W1, int64_t ldw1, int ncols, void* work, int64_t work_bytes,
-                                     double* rn2, double* xn2, ds_stream_t stream) {
-    DS_REQUIRE(R16, "ds_union_residual_pre: null pointer");
-    return union_residual("ds_union_residual_pre", level_tag, utab, ctab, ngroups, cap_blocks, gent, kgrp, mgrp, nnzb, nv, X, ldx, lam,
-                          nullptr, 0, dinv, c, R16, ldr16, W1, ldw1, ncols, work, work_bytes, rn2, xn2, stream);
-}
-
-// Y = K X and Y2 = (M_s (x) I3) X of ONE block in one walk of the unions (spmm_union.inc, epilogue 5): the eigensolver's
-// products of the raw preconditioned residuals W (round 5: Rayleigh-Ritz on the raw basis, csrc/lobpcg.cpp).
-extern "C" int ds_spmm_union_km(int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
-                                const int32_t* gent, const float* kgrp, const float* mgrp, int64_t nnzb, int64_t nv,
-                                const float* X, int64_t ldx, float* KX, int64_t ldk, float* MX, int64_t ldm, int ncols,
-                                ds_stream_t stream) {
-    DS_REQUIRE(ctab && gent && kgrp && mgrp && X && KX && MX, "ds_spmm_union_km: null pointer");
-    DS_REQUIRE(level_tag == 0 || level_tag == 1, "ds_spmm_union_km: level_tag must be 0 (fine) or 1 (corner-node level)");
-    DS_REQUIRE(nv > 0 && ngroups == (nv + 3) / 4 && nnzb > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 84,
-               "ds_spmm_union_km: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / 4)");
-    DS_REQUIRE(cap_blocks > 0 && cap_blocks <= UN_CAPB, "ds_spmm_union_km: a chunk of %d blocks exceeds the LDS image", cap_blocks);
-    DS_REQUIRE(ldx >= ncols && ldk >= ncols && ldm >= ncols, "ds_spmm_union_km: leading dimension smaller than ncols");
-    DS_REQUIRE(X != KX && X != MX && KX != MX, "ds_spmm_union_km: X, KX and MX must be different buffers");
-    DS_REQUIRE(ldx * 12 < (int64_t)PIPE_OOB && nnzb * 36 < ((int64_t)1 << 32), "ds_spmm_union_km: operand beyond the descriptor range");
-    const uintptr_t al = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(KX) | reinterpret_cast<uintptr_t>(MX) |
-                         (uintptr_t)(ldx * 4) | (uintptr_t)(ldk * 4) | (uintptr_t)(ldm * 4) | reinterpret_cast<uintptr_t>(kgrp) |
-                         reinterpret_cast<uintptr_t>(ctab);
-    DS_REQUIRE((al & 15) == 0, "ds_spmm_union_km: rows, kgrp and ctab must be 16-byte aligned");
-    hipStream_t st = ds::as_stream(stream);
-    ChebEpilogue epi{nullptr, ldm, nullptr, 0.f, 0.f, 0};
-    epi.mvals = mgrp, epi.nwork = MX;
-    const int lpn = ncols / 4;
-    ds::ProfScope prof(stream, DS_PROF_KM, nv, nnzb, ncols, 4 << 8);
-#define DS_UKM(L, V) return launch_union<L, 5, false, true, V>(utab, ctab, ngroups, cap_blocks, gent, kgrp, nnzb, nv, X, ldx, KX, ldk, lpn, st, epi)
-    if (lpn == 20) {
-        if (level_tag == 1) DS_UKM(20, 1);
-        DS_UKM(20, 0);
-    }
-    if (level_tag == 1) DS_UKM(0, 1);
-    DS_UKM(0, 0);
-#undef DS_UKM
-}
-
-// bf16-block form of the two preconditioner epilogues (the V-cycle's iterates are stored in bf16, arithmetic in fp32):
-// X, R0, W_prev bf16; Y bf16, or fp32 when y_f32 (the last term of a cycle, written into the solver's basis buffer).
-extern "C" int ds_spmm_union16(int epilogue, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
-                               const int32_t* gent, const float* kgrp, int64_t nnzb, int64_t nv, const void* X,
-                               int64_t ldx, void* Y, int64_t ldy, int y_f32, const void* R0, int64_t ldr,
-                               const float* dinv, int ncols, float c1, float c2, int first, const void* Wprev,
-                               int64_t ldp, ds_stream_t stream) {
-    DS_REQUIRE(ctab && gent && kgrp && X && Y && R0, "ds_spmm_union16: null pointer");
-    DS_REQUIRE(epilogue == 1 || epilogue == 2, "ds_spmm_union16: epilogue must be 1 (Chebyshev term) or 2 (residual)");
-    DS_REQUIRE(epilogue != 1 || dinv, "ds_spmm_union16: the Chebyshev epilogue needs dinv");
-    DS_REQUIRE(nv > 0 && ngroups == (nv + 3) / 4 && nnzb > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 84,
-               "ds_spmm_union16: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / 4)");
-    DS_REQUIRE(cap_blocks > 0 && cap_blocks <= UN_CAPB, "ds_spmm_union16: a chunk of %d blocks exceeds the LDS image", cap_blocks);
-    DS_REQUIRE(ldx >= ncols && ldy >= ncols && ldr >= ncols, "ds_spmm_union16: leading dimension smaller than ncols");
-    DS_REQUIRE(X != Y, "ds_spmm_union16: X and Y must be different buffers");
-    // (the bf16 inputs go through buffer descriptors; the result is stored through plain 64-bit addresses)
-    DS_REQUIRE(3 * nv * std::max(std::max(ldx, ldr), ldp) * 2 < (int64_t)PIPE_OOB && nv * 36 < (int64_t)PIPE_OOB,
-               "ds_spmm_union16: a bf16 operand block of %lld bytes exceeds the descriptor range",
-               (long long)(3 * nv * std::max(std::max(ldx, ldr), ldp) * 2));
-    DS_REQUIRE(nnzb * 36 < ((int64_t)1 << 32), "ds_spmm_union16: value array exceeds the descriptor range");
-    uintptr_t al = reinterpret_cast<uintptr_t>(X) | reinterpret_cast<uintptr_t>(R0) | (uintptr_t)(ldx * 2) | (uintptr_t)(ldr * 2);
-    al |= reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldy * (y_f32 ? 4 : 2));
-    DS_REQUIRE((al & 7) == 0 && (!y_f32 || ((reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldy * 4)) & 15) == 0) &&
-                   ((reinterpret_cast<uintptr_t>(kgrp) | reinterpret_cast<uintptr_t>(ctab)) & 15) == 0,
-               "ds_spmm_union16: bf16 rows must be 8-byte aligned (fp32 output rows, kgrp and ctab 16-byte)");
-    hipStream_t st = ds::as_stream(stream);
-    ChebEpilogue epi{static_cast<const float*>(R0), ldr, dinv, c1, c2, first};
-    if (Wprev && epilogue == 1) {
-        DS_REQUIRE(ldp >= ncols && ((reinterpret_cast<uintptr_t>(Wprev) | (uintptr_t)(ldp * 2)) & 7) == 0 && Wprev != X,
-                   "ds_spmm_union16: bad W_prev block");
-        epi.wprev = static_cast<const float*>(Wprev), epi.ldp = ldp;
-    }
-    DS_REQUIRE(!y_f32 || epilogue == 1, "ds_spmm_union16: an fp32 result is the Chebyshev term's only");
-    const float* Xf = static_cast<const float*>(X);
-    float* Yf = static_cast<float*>(Y);
-    const int lpn = ncols / 4;
-    // (the bf16-in / bf16-out term: the launch the benchmark's roofline figure is about)
-    ds::ProfScope prof((epilogue == 1 && !y_f32) ? stream : nullptr, DS_PROF_TERM, nv, nnzb, ncols, (first ? 1 : 0) | (2 << 8));
-#define DS_U16(L, E, O) return launch_union<L, E, true, O>(utab, ctab, ngroups, cap_blocks, gent, kgrp, nnzb, nv, Xf, ldx, Yf, ldy, lpn, st, epi)
-    if (lpn == 20) {
-        if (epilogue == 2) DS_U16(20, 2, false);
-        if (y_f32) DS_U16(20, 1, true);
-        DS_U16(20, 1, false);
-    }
-    if (epilogue == 2) DS_U16(0, 2, false);
-    if (y_f32) DS_U16(0, 1, true);
-    DS_U16(0, 1, false);
-#undef DS_U16
-}
-
-
-// fp64 values (and fp64 or fp32 vectors) on the neighbour-union tables (spmm_f64_union.inc): the fp64 refinement's K W / M W
-extern "C" int ds_spmm_f64_union(int kind, int x_f64, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
-                                 const int32_t* gent, const double* vals, int64_t nnzb, int64_t nv, const void* X, int64_t ldx,
-                                 double* Y, int64_t ldy, int ncols, ds_stream_t stream) {
-    DS_REQUIRE(ctab && gent && vals && X && Y, "ds_spmm_f64_union: null pointer");
-    DS_REQUIRE(kind == 0 || kind == 1, "ds_spmm_f64_union: kind must be 0 (3x3 blocks in group order, transposed) or 1 (node scalars)");
-    DS_REQUIRE(nv > 0 && ngroups == (nv + 3) / 4 && nnzb > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 84,
-               "ds_spmm_f64_union: ncols must be a multiple of 4 <= 84 and ngroups = ceil(nv / 4)");
-    DS_REQUIRE(cap_blocks > 0 && cap_blocks <= DS_UNION_CAP, "ds_spmm_f64_union: a chunk of %d blocks exceeds the LDS image", cap_blocks);
-    DS_REQUIRE(ldx >= ncols && ldy >= ncols, "ds_spmm_f64_union: leading dimension smaller than ncols");
-    DS_REQUIRE(static_cast<const void*>(Y) != X, "ds_spmm_f64_union: X and Y must be different buffers");
-    const int xb = x_f64 ? 8 : 4;
-    DS_REQUIRE(((reinterpret_cast<uintptr_t>(X) | (uintptr_t)(ldx * xb) | reinterpret_cast<uintptr_t>(Y) | (uintptr_t)(ldy * 8) |
-                 reinterpret_cast<uintptr_t>(ctab)) & 15) == 0, "ds_spmm_f64_union: rows and ctab must be 16-byte aligned");
-    hipStream_t st = ds::as_stream(stream);
-    const unsigned nwg = (unsigned)ds::ceil_div(ngroups, 4);
-    const int lpn = ncols / 4;
-    const int2* ut = reinterpret_cast<const int2*>(utab);
-    const int4* ct = reinterpret_cast<const int4*>(ctab);
-#define DS_F64U(K, T) spmm_f64_union_kernel<K, T><<<nwg, 256, 0, st>>>(ut, ct, (unsigned)ngroups, gent, vals, nv, static_cast<const T*>(X), ldx, Y, ldy, lpn, nwg)
-    if (kind == 0) {
-        if (x_f64) DS_F64U(0, double);
-        else DS_F64U(0, float);
-    } else {
-        if (x_f64) DS_F64U(1, double);
-        else DS_F64U(1, float);
-    }
-#undef DS_F64U
-    DS_LAUNCH_CHECK("spmm_f64_union_kernel");
-    return DS_OK;
-}
-
-// Ya = A X, Yb = B X (fp64 3x3 block values), Ym = (m (x) I3) X (fp64 node scalars) for one fp32 block X in one walk.
-extern "C" int ds_spmm_f64_polish(const int32_t* rowptr, const int32_t* colidx, const double* a, const double* b,
-                                  const double* m, int64_t nv, const float* X, int64_t ldx, double* Ya, double* Yb,
-                                  double* Ym, int64_t ldy, int ncols, ds_stream_t stream) {
-    DS_REQUIRE(rowptr && colidx && a && b && m && X && Ya && Yb && Ym, "ds_spmm_f64_polish: null pointer");
-    DS_REQUIRE(nv > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 84, "ds_spmm_f64_polish: ncols must be a multiple of 4 <= 84");
-    DS_REQUIRE(ldx >= ncols && ldy >= ncols, "ds_spmm_f64_polish: leading dimension smaller than ncols");
-    const uintptr_t ya = reinterpret_cast<uintptr_t>(Ya) | reinterpret_cast<uintptr_t>(Yb) | reinterpret_cast<uintptr_t>(Ym) |
-                         (uintptr_t)(ldy * 8);
-    DS_REQUIRE(((reinterpret_cast<uintptr_t>(X) | (uintptr_t)(ldx * 4) | ya) & 15) == 0,
-               "ds_spmm_f64_polish: rows must be 16-byte aligned");
-    DS_REQUIRE(Ya != Yb && Ya != Ym && Yb != Ym, "ds_spmm_f64_polish: the three results must be different buffers");
-    const unsigned nblk = (unsigned)ds::ceil_div(nv, 4);
-    spmm_f64_polish_kernel<double><<<nblk, 256, 0, ds::as_stream(stream)>>>(rowptr, colidx, a, b, m, nv, X, ldx, Ya, Yb, Ym, ldy,
-                                                                            ncols / 4, nblk);
-    DS_LAUNCH_CHECK("spmm_f64_polish_kernel");
-    return DS_OK;
-}
-
-// the same products, stored as fp32 blocks (sums in fp64, one rounding)
-extern "C" int ds_spmm_f64_polish_f32out(const int32_t* rowptr, const int32_t* colidx, const double* a, const double* b,
-                                         const double* m, int64_t nv, const float* X, int64_t ldx, float* Ya, float* Yb,
-                                         float* Ym, int64_t ldy, int ncols, ds_stream_t stream) {
-    DS_REQUIRE(rowptr && colidx && a && b && m && X && Ya && Yb && Ym, "ds_spmm_f64_polish_f32out: null pointer");
-    DS_REQUIRE(nv > 0 && ncols > 0 && ncols % 4 == 0 && ncols <= 84, "ds_spmm_f64_polish_f32out: ncols must be a multiple of 4 <= 84");
-    DS_REQUIRE(ldx >= ncols && ldy >= ncols, "ds_spmm_f64_polish_f32out: leading dimension smaller than ncols");
-    const uintptr_t ya = reinterpret_cast<uintptr_t>(Ya) | reinterpret_cast<uintptr_t>(Yb) | reinterpret_cast<uintptr_t>(Ym) |
-                         (uintptr_t)(ldy * 4);
-    DS_REQUIRE(((reinterpret_cast<uintptr_t>(X) | (uintptr_t)(ldx * 4) | ya) & 15) == 0,
-               "ds_spmm_f64_polish_f32out: rows must be 16-byte aligned");
-    DS_REQUIRE(Ya != Yb && Ya != Ym && Yb != Ym && Ya != X && Yb != X && Ym != X,
-               "ds_spmm_f64_polish_f32out: X and the three results must be different buffers");
-    const unsigned nblk = (unsigned)ds::ceil_div(nv, 4);
-    spmm_f64_polish_kernel<float><<<nblk, 256, 0, ds::as_stream(stream)>>>(rowptr, colidx, a, b, m, nv, X, ldx, Ya, Yb, Ym, ldy,
-                                                                           ncols / 4, nblk);
-    DS_LAUNCH_CHECK("spmm_f64_polish_kernel<float>");
-    return DS_OK;
 }

@@ -1,5 +1,5 @@
-// Device helpers shared by more than one SpMM translation unit (spmm.hip with its .inc files, spmm_mfma.hip,
-// spmm_mfma32.hip): vector types, the buffer-descriptor words, the bf16 pack / unpack, the non-temporal stream hints and
+// Device helpers shared by more than one SpMM translation unit (spmm.hip, spmm_union.hip with its .inc files,
+// spmm_mfma.hip, spmm_mfma32.hip): vector types, the buffer-descriptor words, the bf16 pack / unpack, the non-temporal stream hints and
 // the epilogue arguments.  What a single unit uses lives in that unit.  Self-contained: it may be a unit's first include.
 #pragma once
 #include "ds_common.h"

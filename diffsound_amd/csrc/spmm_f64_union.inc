@@ -1,5 +1,5 @@
 // fp64 neighbour-union SpMM (round 5): Y = A X with fp64 values AND fp64 (or fp32) vectors, one wave per group of 4 consecutive nodes.
-// Included from spmm.hip inside its anonymous namespace.
+// Included from spmm_f64.hip inside its anonymous namespace.
 //
 // The fp64 refinement's K W / M W (configs[4]) ran on spmm_f64_node_kernel - one wave per NODE, which gathers the 1 920-byte fp64
 // panel of every neighbour of every row: 53 KB of panels per node against 2 KB of coefficients, 73 GB through the L2s per

@@ -1,5 +1,5 @@
-// Neighbour-union SpMM for NARROW blocks (<= 16 columns): Y = K X (3x3 blocks) or Y = (M_s (x) I3) X.  Included from spmm.hip
-// inside its anonymous namespace.
+// Neighbour-union SpMM for NARROW blocks (<= 16 columns): Y = K X (3x3 blocks) or Y = (M_s (x) I3) X.  Included from
+// spmm_union.hip inside its anonymous namespace, after spmm_union.inc.
 //
 // The production kernel (spmm_union.inc) walks a group's union entries ONE AFTER THE OTHER with all 64 lanes on one entry -
 // 3 panel rows x (columns / 4) lanes; on an 8-column block that is 6 busy lanes and a chain of ~62 dependent steps per

@@ -1,5 +1,5 @@
 // Neighbour-union SpMM (the production kernel of the <= 84-column products on both levels) and its inline-asm load /
-// wait helpers.  Included from spmm.hip inside its anonymous namespace, after spmm_device.h.
+// wait helpers.  Included from spmm_union.hip inside its anonymous namespace, after spmm_device.h.
 // Phase B issues its loads through inline asm and waits with explicit counted s_waitcnt: left to the
 // compiler, the FMAs sink below the re-issued loads, the window is renamed into fresh registers and copied
 // back behind a vmcnt(0) at the loop latch (seen in the ISA of the first version of this kernel).  The loaded

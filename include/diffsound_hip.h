@@ -128,7 +128,7 @@ int ds_combine_material(const double* klam, const double* kmu, const double* ms,
                         float* k32, float* k32t, float* ms32, float* dinv32, ds_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Block SpMM  Y = A X  on the BSR-3 pattern (the HBM-roofline kernel).  Replaces torch.sparse.mm
+ * Block SpMM  Y = A X  on the BSR-3 pattern (the HBM-roofline kernel; csrc/spmm.hip).  Replaces torch.sparse.mm
  * in the reference's LOBPCG (src/lobpcg/_linalg_utils.py:36-37) and in get_vals
  * (src/diffelastic/diff_model.py:395-397).
  *   kind 0: A = K,   vals (nnzb x 9) f32           X, Y f32
@@ -199,7 +199,7 @@ int ds_scalar_csr_spmm(const int32_t* rowptr, const int32_t* colidx, const float
 /* The three fp64-value products of the read-out in one walk of the pattern (the panels of X are gathered once instead of
  * three times): Ya = A X, Yb = B X with (nnzb x 9) fp64 blocks (K_lambda, K_mu), Ym = (m (x) I3) X with nnzb fp64 node
  * scalars (M_s); X fp32, results fp64, ncols a multiple of 4 <= 84, 16-byte aligned rows.  Bit-identical to ds_spmm_bsr3
- * kinds 2, 2, 3.  (reference: the autograd read-out of get_undamped_freqs, src/diffelastic/diff_model.py:371-388) */
+ * kinds 2, 2, 3.  csrc/spmm_f64.hip.  (reference: the autograd read-out of get_undamped_freqs, src/diffelastic/diff_model.py:371-388) */
 int ds_spmm_f64_polish(const int32_t* rowptr, const int32_t* colidx, const double* a, const double* b, const double* m,
                        int64_t nv, const float* X, int64_t ldx, double* Ya, double* Yb, double* Ym, int64_t ldy, int ncols,
                        ds_stream_t stream);
@@ -208,7 +208,7 @@ int ds_spmm_f64_polish(const int32_t* rowptr, const int32_t* colidx, const doubl
  * (ds_spmm_bsr3 kinds 4 / 5 gather every neighbour's panel once per ROW: 2.2 x the panels).  vals: kind 0 = the 3x3 blocks in
  * the tables' group order, TRANSPOSED (vals[p][g][i] = A_block[i][g], 9 doubles per block, i.e. ds_pack_groups' layout in fp64);
  * kind 1 = node scalars in that order (A = a (x) I3).  Equal to ds_spmm_bsr3's results to fp64 rounding (another summation order).
- * (reference: torch.sparse.mm of src/lobpcg/_linalg_utils.py:36-37 in fp64) */
+ * csrc/spmm_f64.hip, kernel in spmm_f64_union.inc.  (reference: torch.sparse.mm of src/lobpcg/_linalg_utils.py:36-37 in fp64) */
 int ds_spmm_f64_union(int kind, int x_f64, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
                       const int32_t* gent, const double* vals, int64_t nnzb, int64_t nv, const void* X, int64_t ldx, double* Y,
                       int64_t ldy, int ncols, ds_stream_t stream);
@@ -232,6 +232,7 @@ int ds_pack_groups(const float* vals_t, const int32_t* kperm, int64_t nnzb, floa
  * matrix).  X and Y distinct, 16-byte aligned rows; operand blocks of 2 GB and more (3 nv ld 4 >= 0x7f000000 bytes)
  * take a variant that builds one buffer descriptor per panel load.
  * level_tag (0 fine, 1 corner-node level) selects instantiations of epilogues 0 and 3 whose kernel symbols differ - nothing else.
+ * This and the other fp32 / bf16 walks of these tables: csrc/spmm_union.hip, kernels in spmm_union.inc and spmm_narrow.inc.
  * (reference: torch.sparse.mm in src/lobpcg/_linalg_utils.py:36-37 and the iK callable of _lobpcg.py:441) */
 #define DS_UNION_CAP 140
 int ds_spmm_union(int epilogue, int level_tag, const int32_t* utab, const int32_t* ctab, int64_t ngroups, int cap_blocks,
