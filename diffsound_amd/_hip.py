@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 43  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 44  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -83,6 +83,8 @@ _SIGNATURES = {
     "ds_osc_driven_workspace_bytes": (_I64, [_I, _I, _I]),
     "ds_osc_driven_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
     "ds_osc_driven_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P]),
+    "ds_filtered_noise_fwd": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _P]),
+    "ds_filtered_noise_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),
     "ds_stream_triad": (_I, [_P, _P, _P, _I64, _F, _P]),
     "ds_profile_stream": (_I, [_P, _I64]),
     "ds_profile_collect": (_I64, [_P, _P, _P, _P, _P, _I64]),

@@ -41,7 +41,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 43
+#define DS_ABI_VERSION 44
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -689,6 +689,23 @@ int ds_osc_driven_fwd(const double* d, const double* w, const float* amp, const 
 int ds_osc_driven_bwd(const float* gy, const double* d, const double* w, const float* amp, const float* force, int A, int m,
                       int F, int S, double sr, void* work, int64_t work_bytes, double* gd, double* gw, float* gamp /*or NULL*/,
                       float* gforce /*or NULL, A x F*/, ds_stream_t stream);
+
+/* Filtered-noise branch (ABI 44; reference src/ddsp/filtered_noise.py:20-67, FilteredNoise.forward and its autograd): per
+ * frame of F samples, L logits -> magnitudes -> a Hann-windowed linear-phase FIR of T = 2 L - 1 taps, applied to a white-noise
+ * frame and overlap-added at stride F.  nf = S / F + 1 frames.
+ *   mag[k] = 2 sigmoid(c[k])^2.3 + 1e-6 ;  z[n] = (mag[0] + 2 sum_{k>=1} mag[k] cos(2 pi ((k n) mod T) / T)) / T ;
+ *   h[j] = z[(j - (L - 1)) mod T] (0.5 - 0.5 cos(2 pi j / T)) ;  out[b, f F + s] += gain sum_t noise[b, f, t] h_{b,f}[s - t],
+ *   s < T + F - 1, cut at S.
+ * c (B x nf x L) f32 logits (the module's coefficient_bank), noise (B x nf x F) f32, out, gy (B x S) f32, gc (B x nf x L) f32 =
+ * d / dc of sum gy out.  One launch each; gather forms, no atomics, every output element written exactly once: the same inputs
+ * give the same bits.  The backward reads c, noise and gy only; a frame that starts at or after S gets gc = 0 exactly.
+ * fp32 storage and fp32 convolution sums, fp64 cosine sums and transcendentals (csrc/filtered_noise.hip).  Asynchronous on the
+ * stream, no allocation, no synchronisation.  Refused (DS_ERR_ARG, the message in ds_last_error() names the argument): a null
+ * pointer, L outside [2, 129], F outside [1, 256], S < 1, B outside [1, 65535]. */
+int ds_filtered_noise_fwd(const float* c, const float* noise, int B, int S, int L, int F, double gain, float* out,
+                          ds_stream_t stream);
+int ds_filtered_noise_bwd(const float* gy, const float* c, const float* noise, int B, int S, int L, int F, double gain, float* gc,
+                          ds_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Multi-scale spectral loss head (reference src/ddsp/mss_loss.py:50-62, 70-122: SSSLoss types 'l1_loss' and
