@@ -31,6 +31,13 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nblk) {
     return base + idx;
 }
 
+// Sum of v over the 64 lanes of a wavefront, in every lane (xor butterfly: the same bits in all of them).
+__device__ __forceinline__ double wave_sum(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
 // One row of the first Chebyshev iterate W1 = c T R of the block-Jacobi polynomial: c (da r0 + db r1 + dc r2) on a lane's four
 // columns, (da, db, dc) the row of the node's 3 x 3 block T.  cheb_init16_kernel (precond16.hip) and the residual walk that
 // hands the cycle its inputs (spmm_union.inc, epilogue 6) both call it and must agree to the last bit, so the multiply-adds are

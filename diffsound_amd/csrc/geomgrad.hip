@@ -25,12 +25,6 @@
 
 namespace {
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 template <int N>
 __global__ void __launch_bounds__(256)
     geometry_grad_kernel(const int32_t* __restrict__ tets, int64_t T, const double* __restrict__ tetgeo,
@@ -111,12 +105,12 @@ __global__ void __launch_bounds__(256)
                     dG[k][j] += wg * (P2[0][j] * c[k][0] + P2[1][j] * c[k][1] + P2[2][j] * c[k][2]);
         }
     }
-    sW = wave_sum(sW);
-    sM = wave_sum(sM);
+    sW = ds::wave_sum(sW);
+    sM = ds::wave_sum(sM);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) dG[k][j] = wave_sum(dG[k][j]);
+        for (int j = 0; j < 3; ++j) dG[k][j] = ds::wave_sum(dG[k][j]);
     if (lane != 0) return;
     // s_e = J * sW(G) - J * sM ;  G_3 = -(G_0 + G_1 + G_2) ;  rows of A^-1 are G_0..2
     double B[3][3];
@@ -249,12 +243,12 @@ __global__ void __launch_bounds__(256)
                     dG[k][j] += wg * (P2[j] * c[k][0] + P2[3 + j] * c[k][1] + P2[6 + j] * c[k][2]);
         }
     }
-    sW = wave_sum(sW);
-    sM = wave_sum(sM);
+    sW = ds::wave_sum(sW);
+    sM = ds::wave_sum(sM);
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int j = 0; j < 3; ++j) dG[k][j] = wave_sum(dG[k][j]);
+        for (int j = 0; j < 3; ++j) dG[k][j] = ds::wave_sum(dG[k][j]);
     if (lane != 0) return;
     // as geometry_grad_kernel: s_e = J * sW(G) - J * sM ;  G_3 = -(G_0 + G_1 + G_2) ;  rows of A^-1 are G_0..2
     double B[3][3];

@@ -113,12 +113,6 @@ __device__ __forceinline__ cplx tile_exit(cplx v, cplx carry, cplx zT) {
     return {__shfl(v.r, last, 64) + c.r, __shfl(v.i, last, 64) + c.i};
 }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 // 1. one wavefront per (clip, mode): bnd[(a m + mm) ntiles + k] = the state entering tile k.  in: (A x ldin), zero from nin on.
 template <bool REV>
 __global__ void __launch_bounds__(64)
@@ -234,9 +228,9 @@ __global__ void __launch_bounds__(64)
             G.i += t.i;
         }
     }
-    ga = wave_sum(ga);
-    G.r = wave_sum(G.r);
-    G.i = wave_sum(G.i);
+    ga = ds::wave_sum(ga);
+    G.r = ds::wave_sum(G.r);
+    G.i = ds::wave_sum(G.i);
     if (lane == 0) {
         if (gamp) gamp[(int64_t)a * m + mm] = (float)ga;
         gpart[(int64_t)a * m + mm] = make_double2(am * G.r, am * G.i);
@@ -268,6 +262,17 @@ inline int64_t ntiles_of(int S) { return ds::ceil_div(S, TILE); }
 
 inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
+// The checks both entry points make before those of their own operands' alignment, in their order; `fn` names the entry point
+int check_args(const char* fn, bool pointers, int A, int m, int F, int S, double sr, const void* work, int64_t work_bytes) {
+    DS_REQUIRE(pointers, "%s: null pointer", fn);
+    DS_REQUIRE(A > 0 && m > 0 && S > 0 && F > 0 && sr > 0, "%s: empty problem (A %d, m %d, F %d, S %d)", fn, A, m, F, S);
+    DS_REQUIRE(A <= 65535, "%s: A = %d above 65535", fn, A);
+    DS_REQUIRE(work_bytes >= ds_osc_driven_workspace_bytes(A, m, S), "%s: workspace of %lld bytes, %lld needed", fn,
+               (long long)work_bytes, (long long)ds_osc_driven_workspace_bytes(A, m, S));
+    DS_REQUIRE(aligned(work, 16), "%s: work not 16-byte aligned", fn);
+    return DS_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t ds_osc_driven_workspace_bytes(int A, int m, int S) {
@@ -277,12 +282,7 @@ extern "C" int64_t ds_osc_driven_workspace_bytes(int A, int m, int S) {
 
 extern "C" int ds_osc_driven_fwd(const double* d, const double* w, const float* amp, const float* force, int A, int m,
                                  int F, int S, double sr, void* work, int64_t work_bytes, float* y, ds_stream_t stream) {
-    DS_REQUIRE(d && w && force && work && y, "ds_osc_driven_fwd: null pointer");
-    DS_REQUIRE(A > 0 && m > 0 && S > 0 && F > 0 && sr > 0, "ds_osc_driven_fwd: empty problem (A %d, m %d, F %d, S %d)", A, m, F, S);
-    DS_REQUIRE(A <= 65535, "ds_osc_driven_fwd: A = %d above 65535", A);
-    DS_REQUIRE(work_bytes >= ds_osc_driven_workspace_bytes(A, m, S), "ds_osc_driven_fwd: workspace of %lld bytes, %lld needed",
-               (long long)work_bytes, (long long)ds_osc_driven_workspace_bytes(A, m, S));
-    DS_REQUIRE(aligned(work, 16), "ds_osc_driven_fwd: work not 16-byte aligned");
+    if (int rc = check_args("ds_osc_driven_fwd", d && w && force && work && y, A, m, F, S, sr, work, work_bytes)) return rc;
     DS_REQUIRE(aligned(d, 8) && aligned(w, 8) && aligned(force, 4) && aligned(y, 4) && aligned(amp, 4),
                "ds_osc_driven_fwd: misaligned operand");
     hipStream_t st = ds::as_stream(stream);
@@ -301,12 +301,8 @@ extern "C" int ds_osc_driven_fwd(const double* d, const double* w, const float* 
 extern "C" int ds_osc_driven_bwd(const float* gy, const double* d, const double* w, const float* amp, const float* force,
                                  int A, int m, int F, int S, double sr, void* work, int64_t work_bytes, double* gd, double* gw,
                                  float* gamp, float* gforce, ds_stream_t stream) {
-    DS_REQUIRE(gy && d && w && force && work && gd && gw, "ds_osc_driven_bwd: null pointer");
-    DS_REQUIRE(A > 0 && m > 0 && S > 0 && F > 0 && sr > 0, "ds_osc_driven_bwd: empty problem (A %d, m %d, F %d, S %d)", A, m, F, S);
-    DS_REQUIRE(A <= 65535, "ds_osc_driven_bwd: A = %d above 65535", A);
-    DS_REQUIRE(work_bytes >= ds_osc_driven_workspace_bytes(A, m, S), "ds_osc_driven_bwd: workspace of %lld bytes, %lld needed",
-               (long long)work_bytes, (long long)ds_osc_driven_workspace_bytes(A, m, S));
-    DS_REQUIRE(aligned(work, 16), "ds_osc_driven_bwd: work not 16-byte aligned");
+    if (int rc = check_args("ds_osc_driven_bwd", gy && d && w && force && work && gd && gw, A, m, F, S, sr, work, work_bytes))
+        return rc;
     DS_REQUIRE(aligned(gd, 8) && aligned(gw, 8), "ds_osc_driven_bwd: gd or gw not 8-byte aligned");
     DS_REQUIRE(aligned(d, 8) && aligned(w, 8) && aligned(force, 4) && aligned(gy, 4) && aligned(amp, 4) && aligned(gamp, 4) &&
                    aligned(gforce, 4),

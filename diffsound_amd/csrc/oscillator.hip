@@ -18,6 +18,19 @@ constexpr int TILE = 1024;    // output samples per workgroup
 constexpr int MAXF = 512;     // max force taps
 constexpr int MAXCH = 24;     // max samples per lane per tile: ceil((TILE + MAXF - 1) / 64)
 
+// The tail of both FIR kernels: y[a, t0 + j] = sum_f force[f] sig[H + j - f] for the tile's samples, out of the LDS tile `sig`
+// whose first element is sample t0 - H (H = F - 1)
+__device__ __forceinline__ void fir_from_tile(const float* sig, const float* s_force, int a, int t0, int F, int S, float* y) {
+    const int H = F - 1;
+    const int nout = min(TILE, S - t0);
+    for (int j = threadIdx.x; j < nout; j += blockDim.x) {
+        float acc = 0.f;
+        const float* sp = &sig[H + j];
+        for (int f = 0; f < F; ++f) acc = fmaf(s_force[f], sp[-f], acc);
+        y[(int64_t)a * S + t0 + j] = acc;
+    }
+}
+
 __global__ void __launch_bounds__(256)
     osc_fwd_kernel(const double* __restrict__ dd, const double* __restrict__ ww, const float* __restrict__ amp,
                    const float* __restrict__ force, int m, int F, int S, double inv_sr, float* __restrict__ y) {
@@ -67,13 +80,7 @@ __global__ void __launch_bounds__(256)
     __syncthreads();
     for (int l = threadIdx.x; l < L; l += blockDim.x) s_sig[0][l] = (s_sig[0][l] + s_sig[1][l]) + (s_sig[2][l] + s_sig[3][l]);
     __syncthreads();
-    const int nout = min(TILE, S - t0);
-    for (int j = threadIdx.x; j < nout; j += blockDim.x) {
-        float acc = 0.f;
-        const float* sp = &s_sig[0][H + j];
-        for (int f = 0; f < F; ++f) acc = fmaf(s_force[f], sp[-f], acc);
-        y[(int64_t)a * S + t0 + j] = acc;
-    }
+    fir_from_tile(s_sig[0], s_force, a, t0, F, S, y);
 }
 
 // gs[a,t] = sum_f force[a,f] gy[a,t+f]   (adjoint of the causal FIR + crop)
@@ -90,12 +97,6 @@ __global__ void osc_bwd_corr_kernel(const float* __restrict__ gy, const float* _
     const int fmax = min(F, S - t);
     for (int f = 0; f < fmax; ++f) acc = fmaf(s_force[f], g[t + f], acc);
     gs[(int64_t)a * S + t] = acc;
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // one wavefront per mode: gd = dL/dd_m, gw = dL/dw_m, gamp[a,m] = dL/damp[a,m]
@@ -132,13 +133,13 @@ __global__ void __launch_bounds__(64)
             zr = nr;
             tau += inv_sr;
         }
-        p = wave_sum(p);
+        p = ds::wave_sum(p);
         gd_acc += am * qd;
         gw_acc += am * qw;
         if (gamp && lane == 0) gamp[(int64_t)a * m + mm] = (float)p;
     }
-    gd_acc = wave_sum(gd_acc);
-    gw_acc = wave_sum(gw_acc);
+    gd_acc = ds::wave_sum(gd_acc);
+    gw_acc = ds::wave_sum(gw_acc);
     if (lane == 0) {
         gd[mm] = gd_acc;
         gw[mm] = gw_acc;
@@ -224,13 +225,7 @@ __global__ void __launch_bounds__(256)
         s_sig[l] = v;
     }
     __syncthreads();
-    const int nout = min(TILE, S - t0);
-    for (int j = threadIdx.x; j < nout; j += blockDim.x) {
-        float acc = 0.f;
-        const float* sp = &s_sig[H + j];
-        for (int f = 0; f < F; ++f) acc = fmaf(s_force[f], sp[-f], acc);
-        y[(int64_t)a * S + t0 + j] = acc;
-    }
+    fir_from_tile(s_sig, s_force, a, t0, F, S, y);
 }
 
 // one wavefront per (clip, mode):  with  u_t = gs_t amp e^{-D_t},  gD_t = -u_t sin(2 pi P_t),  gP_t = 2 pi u_t cos(2 pi P_t)
@@ -279,21 +274,36 @@ __global__ void __launch_bounds__(64)
             }
         }
         if (sweep == 0) {
-            totD = wave_sum(totD);
-            totP = wave_sum(totP);
-            ga = wave_sum(ga);
+            totD = ds::wave_sum(totD);
+            totP = ds::wave_sum(totP);
+            ga = ds::wave_sum(ga);
             if (gamp && lane == 0) gamp[(int64_t)a * m + mm] = (float)ga;
         }
     }
+}
+
+// The argument checks of the four entry points, in the order they have always had; `fn` names the entry point.  All of them
+// launch with gridDim.y = A.  (The time-varying pair has A < 65536 in its `nonempty`, the wording its tests pin.)
+int check_args(const char* fn, bool pointers, bool nonempty, int A, int F) {
+    DS_REQUIRE(pointers, "%s: null pointer", fn);
+    DS_REQUIRE(nonempty, "%s: empty problem", fn);
+    DS_REQUIRE(F >= 1 && F <= MAXF, "%s: force length %d not in 1..%d", fn, F, MAXF);
+    DS_REQUIRE(A <= 65535, "%s: A = %d above 65535", fn, A);
+    return DS_OK;
+}
+
+// gs = the force correlated with gy: the first launch of both backward entry points
+int launch_bwd_corr(const float* gy, const float* force, int A, int F, int S, float* gs, hipStream_t st) {
+    osc_bwd_corr_kernel<<<dim3((unsigned)ds::ceil_div(S, 256), (unsigned)A), 256, 0, st>>>(gy, force, F, S, gs);
+    DS_LAUNCH_CHECK("osc_bwd_corr_kernel");
+    return DS_OK;
 }
 
 }  // namespace
 
 extern "C" int ds_osc_bank_fwd(const double* d, const double* w, const float* amp, const float* force, int A, int m,
                                int F, int S, double sr, float* y, ds_stream_t stream) {
-    DS_REQUIRE(d && w && force && y, "ds_osc_bank_fwd: null pointer");
-    DS_REQUIRE(A > 0 && m > 0 && S > 0 && sr > 0, "ds_osc_bank_fwd: empty problem");
-    DS_REQUIRE(F >= 1 && F <= MAXF, "ds_osc_bank_fwd: force length %d not in 1..%d", F, MAXF);
+    if (int rc = check_args("ds_osc_bank_fwd", d && w && force && y, A > 0 && m > 0 && S > 0 && sr > 0, A, F)) return rc;
     dim3 grid((unsigned)ds::ceil_div(S, TILE), (unsigned)A);
     osc_fwd_kernel<<<grid, 256, 0, ds::as_stream(stream)>>>(d, w, amp, force, m, F, S, 1.0 / sr, y);
     DS_LAUNCH_CHECK("osc_fwd_kernel");
@@ -303,13 +313,10 @@ extern "C" int ds_osc_bank_fwd(const double* d, const double* w, const float* am
 extern "C" int ds_osc_bank_bwd(const float* gy, const double* d, const double* w, const float* amp,
                                const float* force, int A, int m, int F, int S, double sr, float* gs, double* gd,
                                double* gw, float* gamp, ds_stream_t stream) {
-    DS_REQUIRE(gy && d && w && force && gs && gd && gw, "ds_osc_bank_bwd: null pointer");
-    DS_REQUIRE(A > 0 && m > 0 && S > 0 && sr > 0, "ds_osc_bank_bwd: empty problem");
-    DS_REQUIRE(F >= 1 && F <= MAXF, "ds_osc_bank_bwd: force length %d not in 1..%d", F, MAXF);
+    if (int rc = check_args("ds_osc_bank_bwd", gy && d && w && force && gs && gd && gw, A > 0 && m > 0 && S > 0 && sr > 0, A, F))
+        return rc;
     hipStream_t st = ds::as_stream(stream);
-    dim3 grid((unsigned)ds::ceil_div(S, 256), (unsigned)A);
-    osc_bwd_corr_kernel<<<grid, 256, 0, st>>>(gy, force, F, S, gs);
-    DS_LAUNCH_CHECK("osc_bwd_corr_kernel");
+    if (int rc = launch_bwd_corr(gy, force, A, F, S, gs, st)) return rc;
     osc_bwd_mode_kernel<<<(unsigned)m, 64, 0, st>>>(gs, d, w, amp, A, m, S, 1.0 / sr, gd, gw, gamp);
     DS_LAUNCH_CHECK("osc_bwd_mode_kernel");
     return DS_OK;
@@ -322,9 +329,8 @@ extern "C" int64_t ds_osc_tv_workspace_floats(int A, int m, int S) {
 
 extern "C" int ds_osc_tv_fwd(const float* dmp, const float* frq, const float* amp, const float* force, int A, int m,
                              int F, int S, double sr, float* work, float* y, ds_stream_t stream) {
-    DS_REQUIRE(dmp && frq && force && work && y, "ds_osc_tv_fwd: null pointer");
-    DS_REQUIRE(A > 0 && A < 65536 && m > 0 && S > 0 && sr > 0, "ds_osc_tv_fwd: empty problem");
-    DS_REQUIRE(F >= 1 && F <= MAXF, "ds_osc_tv_fwd: force length %d not in 1..%d", F, MAXF);
+    if (int rc = check_args("ds_osc_tv_fwd", dmp && frq && force && work && y, A > 0 && A < 65536 && m > 0 && S > 0 && sr > 0, A, F))
+        return rc;
     hipStream_t st = ds::as_stream(stream);
     const int ng = (int)ds::ceil_div(m, TV_MPG);
     osc_tv_modes_kernel<<<dim3((unsigned)ng, (unsigned)A), 256, 0, st>>>(dmp, frq, amp, m, S, 1.0 / sr, work);
@@ -337,12 +343,11 @@ extern "C" int ds_osc_tv_fwd(const float* dmp, const float* frq, const float* am
 extern "C" int ds_osc_tv_bwd(const float* gy, const float* dmp, const float* frq, const float* amp, const float* force,
                              int A, int m, int F, int S, double sr, float* gs, float* g_dmp, float* g_frq, float* gamp,
                              ds_stream_t stream) {
-    DS_REQUIRE(gy && dmp && frq && force && gs && g_dmp && g_frq, "ds_osc_tv_bwd: null pointer");
-    DS_REQUIRE(A > 0 && A < 65536 && m > 0 && S > 0 && sr > 0, "ds_osc_tv_bwd: empty problem");
-    DS_REQUIRE(F >= 1 && F <= MAXF, "ds_osc_tv_bwd: force length %d not in 1..%d", F, MAXF);
+    if (int rc = check_args("ds_osc_tv_bwd", gy && dmp && frq && force && gs && g_dmp && g_frq,
+                            A > 0 && A < 65536 && m > 0 && S > 0 && sr > 0, A, F))
+        return rc;
     hipStream_t st = ds::as_stream(stream);
-    osc_bwd_corr_kernel<<<dim3((unsigned)ds::ceil_div(S, 256), (unsigned)A), 256, 0, st>>>(gy, force, F, S, gs);
-    DS_LAUNCH_CHECK("osc_bwd_corr_kernel");
+    if (int rc = launch_bwd_corr(gy, force, A, F, S, gs, st)) return rc;
     osc_tv_bwd_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(gs, dmp, frq, amp, m, S, 1.0 / sr, g_dmp, g_frq, gamp);
     DS_LAUNCH_CHECK("osc_tv_bwd_kernel");
     return DS_OK;

@@ -1,0 +1,150 @@
+"""The oscillator banks as functions of tensors: three ``torch.autograd.Function`` wrappers, one per kernel family, and their
+functional entries.  ``_OscBank`` is the closed-form bank with the force as a causal FIR out of LDS (ds_osc_bank_fwd / _bwd,
+csrc/oscillator.hip), ``_OscBankTV`` the bank with per-sample rates (ds_osc_tv_fwd / _bwd, same file), ``_OscDriven`` the
+recursive resonator under a force of any length, with a force gradient (ds_osc_driven_fwd / _bwd, csrc/osc_driven.hip).
+What the three share - operand preparation, the optional ``amp`` across save_for_backward, the gradient buffers - is written
+once below; a ``forward`` / ``backward`` holds its entry point, its workspace and its extra gradient."""
+import torch
+
+from .. import _hip
+
+FIR_MAX_FORCE = 512  # taps the FIR kernels of csrc/oscillator.hip hold in LDS (MAXF)
+
+
+def _prepare(dtype, d, w, amp, force):
+    """The kernels' operands: on the device, detached, contiguous; d and w (the per-mode pair) in ``dtype``, amp (or None)
+    and force fp32."""
+    _hip.require_gpu(d, w, force, amp)
+    return (d.detach().to(dtype).contiguous(), w.detach().to(dtype).contiguous(),
+            None if amp is None else amp.detach().float().contiguous(), force.detach().float().contiguous())
+
+
+def _save(ctx, d, w, amp, force, S, sr):
+    """save_for_backward takes tensors: an absent amp goes in as an empty sentinel and a flag."""
+    ctx.save_for_backward(d, w, force, amp if amp is not None else torch.empty(0, device=force.device))
+    ctx.has_amp = amp is not None
+    ctx.S, ctx.sr = S, float(sr)
+
+
+def _restore(ctx, gy):
+    """(d, w, amp or None, force) as saved, and gy as the kernels take it."""
+    d, w, force, amp = ctx.saved_tensors
+    return d, w, (amp if ctx.has_amp else None), force, gy.float().contiguous()
+
+
+def _grad_buffers(d, w, amp):
+    """Uninitialised gradients of d, w and, where there is one, amp: the kernels write every element."""
+    return torch.empty_like(d), torch.empty_like(w), (None if amp is None else torch.empty_like(amp))
+
+
+class _OscBank(torch.autograd.Function):
+    """y[a,t] = sum_j force[a,j] sum_m amp[a,m] exp(-d_m tau) sin(w_m tau) at tau = (t-j+1)/sr."""
+
+    @staticmethod
+    def forward(ctx, d, w, amp, force, S, sr):
+        d, w, amp, force = _prepare(torch.float64, d, w, amp, force)
+        A, nF = force.shape
+        y = torch.empty((A, S), dtype=torch.float32, device=force.device)
+        p = _hip.ptr
+        _hip.check(_hip.lib().ds_osc_bank_fwd(p(d), p(w), p(amp), p(force), A, d.shape[0], nF, S, float(sr), p(y),
+                                              _hip.stream_ptr()), "ds_osc_bank_fwd")
+        _save(ctx, d, w, amp, force, S, sr)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        d, w, amp, force, gy = _restore(ctx, gy)
+        A, nF = force.shape
+        gs = torch.empty_like(gy)
+        gd, gw, gamp = _grad_buffers(d, w, amp)
+        p = _hip.ptr
+        _hip.check(_hip.lib().ds_osc_bank_bwd(p(gy), p(d), p(w), p(amp), p(force), A, d.shape[0], nF, ctx.S, ctx.sr, p(gs),
+                                              p(gd), p(gw), p(gamp), _hip.stream_ptr()), "ds_osc_bank_bwd")
+        return gd, gw, gamp, None, None, None
+
+
+class _OscBankTV(torch.autograd.Function):
+    """Time-varying bank: y = FIR(sum_m amp exp(-cumsum(dmp / sr)) sin(2 pi cumsum(frq / sr))), dmp / frq (A, m, S)."""
+
+    @staticmethod
+    def forward(ctx, dmp, frq, amp, force, S, sr):
+        dmp, frq, amp, force = _prepare(torch.float32, dmp, frq, amp, force)
+        A, m, S_ = dmp.shape
+        if S_ != S or frq.shape != dmp.shape or force.shape[0] != A:
+            raise ValueError("time-varying bank: dmp and frq must be (audio_num, mode_num, sample_num)")
+        L = _hip.lib()
+        work = torch.empty(L.ds_osc_tv_workspace_floats(A, m, S), dtype=torch.float32, device=dmp.device)
+        y = torch.empty((A, S), dtype=torch.float32, device=dmp.device)
+        p = _hip.ptr
+        _hip.check(L.ds_osc_tv_fwd(p(dmp), p(frq), p(amp), p(force), A, m, force.shape[1], S, float(sr), p(work), p(y),
+                                   _hip.stream_ptr()), "ds_osc_tv_fwd")
+        _save(ctx, dmp, frq, amp, force, S, sr)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        dmp, frq, amp, force, gy = _restore(ctx, gy)
+        A, m, S = dmp.shape
+        gs = torch.empty_like(gy)
+        gd, gf, gamp = _grad_buffers(dmp, frq, amp)
+        p = _hip.ptr
+        _hip.check(_hip.lib().ds_osc_tv_bwd(p(gy), p(dmp), p(frq), p(amp), p(force), A, m, force.shape[1], S, ctx.sr,
+                                            p(gs), p(gd), p(gf), p(gamp), _hip.stream_ptr()), "ds_osc_tv_bwd")
+        return gd, gf, gamp, None, None, None
+
+
+class _OscDriven(torch.autograd.Function):
+    """The same y as ``_OscBank`` from the recursive resonator x[t] = z (x[t-1] + force[t]) per mode (ds_osc_driven_fwd /
+    ds_osc_driven_bwd): any force length, gradients for d, w, amp and force."""
+
+    @staticmethod
+    def _work(L, A, m, S, device):
+        nbytes = L.ds_osc_driven_workspace_bytes(A, m, S)
+        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+    @staticmethod
+    def forward(ctx, d, w, amp, force, S, sr):
+        d, w, amp, force = _prepare(torch.float64, d, w, amp, force)
+        A, nF = force.shape
+        m = d.shape[0]
+        L = _hip.lib()
+        work, nbytes = _OscDriven._work(L, A, m, S, force.device)
+        y = torch.empty((A, S), dtype=torch.float32, device=force.device)
+        p = _hip.ptr
+        _hip.check(L.ds_osc_driven_fwd(p(d), p(w), p(amp), p(force), A, m, nF, S, float(sr), p(work), nbytes, p(y),
+                                       _hip.stream_ptr()), "ds_osc_driven_fwd")
+        _save(ctx, d, w, amp, force, S, sr)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        d, w, amp, force, gy = _restore(ctx, gy)
+        A, nF = force.shape
+        m = d.shape[0]
+        L = _hip.lib()
+        work, nbytes = _OscDriven._work(L, A, m, ctx.S, gy.device)
+        gd, gw, gamp = _grad_buffers(d, w, amp)
+        gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
+        p = _hip.ptr
+        _hip.check(L.ds_osc_driven_bwd(p(gy), p(d), p(w), p(amp), p(force), A, m, nF, ctx.S, ctx.sr, p(work), nbytes, p(gd),
+                                       p(gw), p(gamp), p(gforce), _hip.stream_ptr()), "ds_osc_driven_bwd")
+        return gd, gw, gamp, gforce, None, None
+
+
+def oscillator_bank_tv(dmp, frq, amp, force, sample_num, sr):
+    """Functional entry of the time-varying bank: dmp [1/s], frq [Hz] (A, m, S) HIP tensors (autograd ok)."""
+    return _OscBankTV.apply(dmp, frq, amp, force, int(sample_num), float(sr))
+
+
+def oscillator_bank_driven(d, w, amp, force, sample_num, sr):
+    """``oscillator_bank`` on the recursive-resonator kernels whatever the force length (tests, measurement)."""
+    return _OscDriven.apply(d, w, amp, force, int(sample_num), float(sr))
+
+
+def oscillator_bank(d, w, amp, force, sample_num, sr):
+    """Functional entry: d, w (m,) fp64 HIP tensors (autograd ok), amp (A,m) or None, force (A,F), any F >= 1.
+    Up to 512 taps without a force gradient this is the FIR bank (ds_osc_bank_fwd / _bwd); a longer force, or one that
+    requires grad, goes through the driven bank (ds_osc_driven_fwd / _bwd), which also returns the force gradient."""
+    if force.shape[-1] <= FIR_MAX_FORCE and not force.requires_grad:
+        return _OscBank.apply(d, w, amp, force, int(sample_num), float(sr))
+    return _OscDriven.apply(d, w, amp, force, int(sample_num), float(sr))

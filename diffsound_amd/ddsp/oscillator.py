@@ -8,20 +8,23 @@ kernels (``ds_osc_driven_fwd`` / ``ds_osc_driven_bwd``), which also return the f
 The tiny per-mode parameter algebra (softplus-weighted bins, d = (alpha + beta w0^2)/2,
 w = sqrt(w0^2 - d^2)) stays in torch so autograd reaches every learnable leaf exactly as in the
 reference.
+
+This file holds the parameter modules and the ``nn.Module`` banks.  The autograd Functions and the functional entries
+(``oscillator_bank`` ...) live in ``bank.py``, ``FilteredNoise`` in ``filtered_noise.py`` and ``modifed_sigmoid`` in
+``utils.py`` (the last two as in the reference); every name that used to be defined here is still importable from here.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import _hip
+from .. import _hip  # noqa: F401
 from ..diffelastic.material_model import Material, MatSet  # noqa: F401  (re-exported like the reference)
-
-
-def modifed_sigmoid(x):
-    """reference src/ddsp/utils.py:6-9 (spelling kept)."""
-    return 2 * (torch.sigmoid(x) ** 2.3) + 1e-6
-
+from .bank import (FIR_MAX_FORCE, _OscBank, _OscBankTV, _OscDriven, oscillator_bank, oscillator_bank_driven,  # noqa: F401
+                   oscillator_bank_tv)
+from .filtered_noise import (FN_MAX_COEFF, FN_MAX_FRAME, FilteredNoise, _FilteredNoiseFn,  # noqa: F401
+                             _filtered_noise_torch)
+from .utils import modifed_sigmoid
 
 class WeightedParam(nn.Module):
     """Scalar = sum_j v_j softplus(p_j) / sum softplus(p)  (reference oscillator.py:10-21)."""
@@ -65,236 +68,6 @@ class DirectValue(nn.Module):
 
     def forward(self):
         return modifed_sigmoid(self.value)
-
-
-FN_MAX_COEFF, FN_MAX_FRAME = 129, 256  # filter_coeff_length / frame_length csrc/filtered_noise.hip holds in LDS
-
-
-def _filtered_noise_torch(bank, noise, sample_num, frame_length, attenuate_gain):
-    """The reference's formulation (src/ddsp/filtered_noise.py:20-67) op by op, torch.fft plumbing: CPU tensors, sizes
-    outside the native range, and a noise that itself requires grad."""
-    mag = modifed_sigmoid(bank)
-    B, nf, L = mag.shape
-    taps = 2 * L - 1
-    ir = torch.fft.irfft(torch.complex(mag, torch.zeros_like(mag)), n=taps, dim=-1)  # zero-phase
-    ir = torch.roll(ir, L - 1, dims=-1) * torch.hann_window(taps, dtype=torch.float32, device=mag.device)
-    nfft = taps + frame_length - 1
-    frames = torch.fft.irfft(torch.fft.rfft(noise, n=nfft) * torch.fft.rfft(ir, n=nfft), n=nfft)
-    frames = frames * attenuate_gain
-    total = (nf - 1) * frame_length + nfft
-    out = F.fold(frames.transpose(1, 2), output_size=(1, total), kernel_size=(1, nfft),
-                 stride=(1, frame_length)).reshape(B, total)
-    return out[:, :sample_num]
-
-
-class _FilteredNoiseFn(torch.autograd.Function):
-    """out (B, S) = overlap-add of gain (noise_f * h_f), h_f the Hann-windowed linear-phase FIR of bank[:, f]
-    (ds_filtered_noise_fwd / ds_filtered_noise_bwd, one launch each); the gradient goes to the bank only."""
-
-    @staticmethod
-    def forward(ctx, bank, noise, S, frame_length, gain):
-        _hip.require_gpu(bank, noise)
-        bank = bank.detach().float().contiguous()
-        noise = noise.detach().float().contiguous()
-        B, nf, L = bank.shape
-        if nf != S // frame_length + 1 or noise.shape != (B, nf, frame_length):
-            raise ValueError(f"filtered noise: bank {tuple(bank.shape)} / noise {tuple(noise.shape)} do not fit "
-                             f"(noise_num, {S // frame_length + 1}, filter_coeff_length / {frame_length})")
-        out = torch.empty((B, S), dtype=torch.float32, device=bank.device)
-        p = _hip.ptr
-        _hip.check(_hip.lib().ds_filtered_noise_fwd(p(bank), p(noise), B, S, L, frame_length, float(gain), p(out),
-                                                    _hip.stream_ptr()), "ds_filtered_noise_fwd")
-        ctx.save_for_backward(bank, noise)
-        ctx.S, ctx.frame_length, ctx.gain = S, frame_length, float(gain)
-        return out
-
-    @staticmethod
-    def backward(ctx, gy):
-        bank, noise = ctx.saved_tensors
-        B, nf, L = bank.shape
-        gy = gy.float().contiguous()
-        gc = torch.empty_like(bank)
-        p = _hip.ptr
-        _hip.check(_hip.lib().ds_filtered_noise_bwd(p(gy), p(bank), p(noise), B, ctx.S, L, ctx.frame_length, ctx.gain, p(gc),
-                                                    _hip.stream_ptr()), "ds_filtered_noise_bwd")
-        return gc, None, None, None, None
-
-
-class FilteredNoise(nn.Module):
-    """Time-varying filtered white noise (DDSP style): per 64-sample frame a learnable magnitude response
-    (65 bins) is turned into a Hann-windowed linear-phase FIR, applied to a fresh white-noise frame, and the frames are
-    overlap-added.  Interface of reference src/ddsp/filtered_noise.py:7-67 (``coefficient_bank`` parameter,
-    ``forward() -> (noise_num, sample_num)``).  On a HIP device, with ``filter_coeff_length`` in [2, 129] and
-    ``frame_length`` in [1, 256], the whole map is ONE kernel forward and one backward (ds_filtered_noise_fwd / _bwd:
-    direct sums, no FFT, no temporaries, deterministic; the gradient reaches ``coefficient_bank``); CPU tensors, other
-    sizes and an injected noise that requires grad take the reference's torch.fft formulation."""
-
-    def __init__(self, noise_num, sample_num, filter_coeff_length=65, frame_length=64, attenuate_gain=1.0,
-                 device="cuda"):
-        super().__init__()
-        self.noise_num, self.sample_num = noise_num, sample_num
-        self.filter_coeff_length, self.frame_length, self.attenuate_gain = filter_coeff_length, frame_length, attenuate_gain
-        self.coefficient_bank = nn.Parameter(torch.zeros(noise_num, sample_num // frame_length + 1, filter_coeff_length))
-        self.coefficient_bank.data.uniform_(-1, 1)
-
-    def forward(self, noise=None):
-        """noise: optional (noise_num, frames, frame_length) tensor in [-1, 1) replacing the internal draw (tests)."""
-        bank = self.coefficient_bank
-        B, nf, L = bank.shape
-        if noise is None:
-            noise = torch.rand(B, nf, self.frame_length, device=bank.device) * 2 - 1
-        native = (bank.is_cuda and noise.is_cuda and not noise.requires_grad and self.sample_num >= 1
-                  and 2 <= L <= FN_MAX_COEFF and 1 <= self.frame_length <= FN_MAX_FRAME)
-        if native:
-            return _FilteredNoiseFn.apply(bank, noise, int(self.sample_num), int(self.frame_length), float(self.attenuate_gain))
-        return _filtered_noise_torch(bank, noise, self.sample_num, self.frame_length, self.attenuate_gain)
-
-
-class _OscBank(torch.autograd.Function):
-    """y[a,t] = sum_j force[a,j] sum_m amp[a,m] exp(-d_m tau) sin(w_m tau) at tau = (t-j+1)/sr."""
-
-    @staticmethod
-    def forward(ctx, d, w, amp, force, S, sr):
-        _hip.require_gpu(d, w, force, amp)
-        d = d.detach().double().contiguous()
-        w = w.detach().double().contiguous()
-        force = force.detach().float().contiguous()
-        ampc = None if amp is None else amp.detach().float().contiguous()
-        A, nF = force.shape
-        m = d.shape[0]
-        y = torch.empty((A, S), dtype=torch.float32, device=force.device)
-        p = _hip.ptr
-        _hip.check(_hip.lib().ds_osc_bank_fwd(p(d), p(w), p(ampc), p(force), A, m, nF, S, float(sr), p(y),
-                                              _hip.stream_ptr()), "ds_osc_bank_fwd")
-        ctx.save_for_backward(d, w, force, ampc if ampc is not None else torch.empty(0, device=force.device))
-        ctx.has_amp = ampc is not None
-        ctx.S, ctx.sr = S, float(sr)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        d, w, force, ampc = ctx.saved_tensors
-        amp = ampc if ctx.has_amp else None
-        A, nF = force.shape
-        m = d.shape[0]
-        gy = gy.float().contiguous()
-        gs = torch.empty_like(gy)
-        gd = torch.empty(m, dtype=torch.float64, device=gy.device)
-        gw = torch.empty(m, dtype=torch.float64, device=gy.device)
-        gamp = torch.empty((A, m), dtype=torch.float32, device=gy.device) if amp is not None else None
-        p = _hip.ptr
-        _hip.check(_hip.lib().ds_osc_bank_bwd(p(gy), p(d), p(w), p(amp), p(force), A, m, nF, ctx.S, ctx.sr, p(gs),
-                                              p(gd), p(gw), p(gamp), _hip.stream_ptr()), "ds_osc_bank_bwd")
-        return gd, gw, gamp, None, None, None
-
-
-class _OscBankTV(torch.autograd.Function):
-    """Time-varying bank: y = FIR(sum_m amp exp(-cumsum(dmp / sr)) sin(2 pi cumsum(frq / sr))), dmp / frq (A, m, S)."""
-
-    @staticmethod
-    def forward(ctx, dmp, frq, amp, force, S, sr):
-        _hip.require_gpu(dmp, frq, force, amp)
-        dmp = dmp.detach().float().contiguous()
-        frq = frq.detach().float().contiguous()
-        force = force.detach().float().contiguous()
-        ampc = None if amp is None else amp.detach().float().contiguous()
-        A, m, S_ = dmp.shape
-        if S_ != S or frq.shape != dmp.shape or force.shape[0] != A:
-            raise ValueError("time-varying bank: dmp and frq must be (audio_num, mode_num, sample_num)")
-        L = _hip.lib()
-        work = torch.empty(L.ds_osc_tv_workspace_floats(A, m, S), dtype=torch.float32, device=dmp.device)
-        y = torch.empty((A, S), dtype=torch.float32, device=dmp.device)
-        p = _hip.ptr
-        _hip.check(L.ds_osc_tv_fwd(p(dmp), p(frq), p(ampc), p(force), A, m, force.shape[1], S, float(sr), p(work), p(y),
-                                   _hip.stream_ptr()), "ds_osc_tv_fwd")
-        ctx.save_for_backward(dmp, frq, force, ampc if ampc is not None else torch.empty(0, device=dmp.device))
-        ctx.has_amp = ampc is not None
-        ctx.sr = float(sr)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        dmp, frq, force, ampc = ctx.saved_tensors
-        amp = ampc if ctx.has_amp else None
-        A, m, S = dmp.shape
-        gy = gy.float().contiguous()
-        gs = torch.empty_like(gy)
-        gd, gf = torch.empty_like(dmp), torch.empty_like(frq)
-        gamp = torch.empty((A, m), dtype=torch.float32, device=gy.device) if amp is not None else None
-        p = _hip.ptr
-        _hip.check(_hip.lib().ds_osc_tv_bwd(p(gy), p(dmp), p(frq), p(amp), p(force), A, m, force.shape[1], S, ctx.sr,
-                                            p(gs), p(gd), p(gf), p(gamp), _hip.stream_ptr()), "ds_osc_tv_bwd")
-        return gd, gf, gamp, None, None, None
-
-
-def oscillator_bank_tv(dmp, frq, amp, force, sample_num, sr):
-    """Functional entry of the time-varying bank: dmp [1/s], frq [Hz] (A, m, S) HIP tensors (autograd ok)."""
-    return _OscBankTV.apply(dmp, frq, amp, force, int(sample_num), float(sr))
-
-
-class _OscDriven(torch.autograd.Function):
-    """The same y as ``_OscBank`` from the recursive resonator x[t] = z (x[t-1] + force[t]) per mode (ds_osc_driven_fwd /
-    ds_osc_driven_bwd): any force length, gradients for d, w, amp and force."""
-
-    @staticmethod
-    def _work(L, A, m, S, device):
-        nbytes = L.ds_osc_driven_workspace_bytes(A, m, S)
-        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
-
-    @staticmethod
-    def forward(ctx, d, w, amp, force, S, sr):
-        _hip.require_gpu(d, w, force, amp)
-        d = d.detach().double().contiguous()
-        w = w.detach().double().contiguous()
-        force = force.detach().float().contiguous()
-        ampc = None if amp is None else amp.detach().float().contiguous()
-        A, nF = force.shape
-        m = d.shape[0]
-        L = _hip.lib()
-        work, nbytes = _OscDriven._work(L, A, m, S, force.device)
-        y = torch.empty((A, S), dtype=torch.float32, device=force.device)
-        p = _hip.ptr
-        _hip.check(L.ds_osc_driven_fwd(p(d), p(w), p(ampc), p(force), A, m, nF, S, float(sr), p(work), nbytes, p(y),
-                                       _hip.stream_ptr()), "ds_osc_driven_fwd")
-        ctx.save_for_backward(d, w, force, ampc if ampc is not None else torch.empty(0, device=force.device))
-        ctx.has_amp = ampc is not None
-        ctx.S, ctx.sr = S, float(sr)
-        return y
-
-    @staticmethod
-    def backward(ctx, gy):
-        d, w, force, ampc = ctx.saved_tensors
-        amp = ampc if ctx.has_amp else None
-        A, nF = force.shape
-        m = d.shape[0]
-        gy = gy.float().contiguous()
-        L = _hip.lib()
-        work, nbytes = _OscDriven._work(L, A, m, ctx.S, gy.device)
-        gd = torch.empty(m, dtype=torch.float64, device=gy.device)
-        gw = torch.empty(m, dtype=torch.float64, device=gy.device)
-        gamp = torch.empty((A, m), dtype=torch.float32, device=gy.device) if amp is not None else None
-        gforce = torch.empty((A, nF), dtype=torch.float32, device=gy.device) if ctx.needs_input_grad[3] else None
-        p = _hip.ptr
-        _hip.check(L.ds_osc_driven_bwd(p(gy), p(d), p(w), p(amp), p(force), A, m, nF, ctx.S, ctx.sr, p(work), nbytes, p(gd),
-                                       p(gw), p(gamp), p(gforce), _hip.stream_ptr()), "ds_osc_driven_bwd")
-        return gd, gw, gamp, gforce, None, None
-
-
-FIR_MAX_FORCE = 512  # taps the FIR kernels of csrc/oscillator.hip hold in LDS (MAXF)
-
-
-def oscillator_bank_driven(d, w, amp, force, sample_num, sr):
-    """``oscillator_bank`` on the recursive-resonator kernels whatever the force length (tests, measurement)."""
-    return _OscDriven.apply(d, w, amp, force, int(sample_num), float(sr))
-
-
-def oscillator_bank(d, w, amp, force, sample_num, sr):
-    """Functional entry: d, w (m,) fp64 HIP tensors (autograd ok), amp (A,m) or None, force (A,F), any F >= 1.
-    Up to 512 taps without a force gradient this is the FIR bank (ds_osc_bank_fwd / _bwd); a longer force, or one that
-    requires grad, goes through the driven bank (ds_osc_driven_fwd / _bwd), which also returns the force gradient."""
-    if force.shape[-1] <= FIR_MAX_FORCE and not force.requires_grad:
-        return _OscBank.apply(d, w, amp, force, int(sample_num), float(sr))
-    return _OscDriven.apply(d, w, amp, force, int(sample_num), float(sr))
 
 
 def _device_of(t):

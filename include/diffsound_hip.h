@@ -628,6 +628,7 @@ int ds_geometry_grad_tangent(const int32_t* tets, int64_t T, int N, int64_t nv, 
  * d, w: (m) f64 (decay rate and damped angular frequency) ; amp: (A x m) f32 or NULL (= 1) ;
  * force: (A x F) f32 ; y: (A x S) f32.
  * Backward: gy (A x S) f32 -> gd, gw (m) f64, gamp (A x m) f32 (may be NULL) ; gs is scratch (A x S) f32.
+ * 1 <= F <= 512 and A <= 65535 (A is a grid dimension); anything else is refused with DS_ERR_ARG.
  * ---------------------------------------------------------------------------------------------- */
 int ds_osc_bank_fwd(const double* d, const double* w, const float* amp, const float* force,
                     int A, int m, int F, int S, double sr, float* y, ds_stream_t stream);

@@ -1,5 +1,6 @@
-"""Guard zones for kernel outputs in GPU tests (not a test module): an output placed PAD elements inside a NaN-filled
-device buffer, so that a write before its start or past its end, or an element left unwritten, is seen after the call."""
+"""What the kernel tests share (not a test module).  Guard zones for kernel outputs: an output placed PAD elements inside a
+NaN-filled device buffer, so that a write before its start or past its end, or an element left unwritten, is seen after the
+call.  And the small helpers: the library handle, uploads, case ids and the printed error / bound ratio."""
 import numpy as np
 import torch
 
@@ -9,6 +10,31 @@ PAD = 64
 def dev():
     assert torch.cuda.is_available(), "needs a HIP device"
     return torch.device("cuda:0")
+
+
+def _lib():
+    from diffsound_amd import _hip
+
+    return _hip, _hip.lib()
+
+
+def _up(x):
+    return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(dev())
+
+
+def _id(case):
+    """A case tuple, with any shape tuple inside it spread out, joined by dashes: ((1, 5), "base") -> 1-5-base."""
+    return "-".join(str(v) for c in case for v in (c if isinstance(c, tuple) else (c,)))
+
+
+def _ratio(tag, case, got, ref, bound):
+    """Largest |got - ref| / bound, printed as ``RATIO <tag> <case> <value>`` (no case: None); a zero bound admits only an
+    exact match."""
+    err = np.abs(np.asarray(got, dtype=np.float64) - ref)
+    r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, np.inf))
+    worst = float(r.max())
+    print(f"RATIO {tag} {_id(case)} {worst:.4g}" if case is not None else f"RATIO {tag} {worst:.4g}")
+    return worst
 
 
 class Guarded:

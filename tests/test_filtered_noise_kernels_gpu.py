@@ -26,38 +26,15 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _filtered_noise_ref as R  # noqa: E402
-from _guarded import PAD, Guarded, dev as _dev  # noqa: E402
+from _guarded import PAD, Guarded, _id, _lib, _ratio, _up, dev as _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 CASES = [(c, g) for c in R.SHAPES for g in R.GAINS]
 
 
-def _id(case):
-    return "-".join(map(str, case))
-
-
 def _cid(p):
     return f"{_id(p[0])}-gain{p[1]}"
-
-
-def _up(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(_dev())
-
-
-def _ratio(tag, case, got, ref, bound):
-    """Largest |got - ref| / bound; a zero bound admits only an exact match."""
-    err = np.abs(np.asarray(got, dtype=np.float64) - ref)
-    r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, np.inf))
-    worst = float(r.max())
-    print(f"RATIO {tag} {_id(case)} {worst:.4g}")
-    return worst
-
-
-def _lib():
-    from diffsound_amd import _hip
-
-    return _hip, _hip.lib()
 
 
 def _fwd_call(d_c, d_noise, B, L, F, S, gain):

@@ -26,15 +26,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _filtered_noise_ref as R  # noqa: E402
+from _guarded import _id  # noqa: E402
 from oracle import oscillator as oosc  # noqa: E402
 
 FP64_TOL = 1e-13
 GOLDEN_TOL = 2e-6
 CASES = [(c, g) for c in R.SHAPES for g in R.GAINS]
-
-
-def _id(case):
-    return "-".join(map(str, case))
 
 
 def _cid(p):

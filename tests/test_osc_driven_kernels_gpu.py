@@ -15,31 +15,12 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _osc_driven_ref as D  # noqa: E402
-from _guarded import Guarded, dev as _dev  # noqa: E402
+from _guarded import Guarded, _lib, _ratio, _up, dev as _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SR = D.SR
 IDS = [D.case_id(c) for c in D.CASES]
-
-
-def _lib():
-    from diffsound_amd import _hip
-
-    return _hip, _hip.lib()
-
-
-def _up(x):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(_dev())
-
-
-def _ratio(tag, case, got, ref, bound):
-    """Largest |got - ref| / bound; a zero bound admits only an exact match."""
-    err = np.abs(np.asarray(got, dtype=np.float64) - ref)
-    r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, np.inf))
-    worst = float(r.max()) if r.size else 0.0
-    print(f"RATIO {tag} {D.case_id(case)} {worst:.4g}")
-    return worst
 
 
 def _call(case, inputs):

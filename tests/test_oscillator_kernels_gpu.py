@@ -14,36 +14,13 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _osc_ref as R  # noqa: E402
-from _guarded import Guarded, dev as _dev  # noqa: E402
+from _guarded import Guarded, _id, _lib, _ratio, _up, dev as _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 SR = R.SR
 TV_CASES = [(s, "base") for s in R.TV_SHAPES] + [(s, v) for s in R.TV_SHAPES if s[3] in (65, 1025) for v in R.TV_VARIANTS]
 BANK_CASES = [(s, True) for s in R.BANK_SHAPES] + [(R.BANK_SHAPES[i], False) for i in (0, 3, 5)]
-
-
-def _id(case):
-    return "-".join(map(str, case[0])) + "-" + str(case[1])
-
-
-def _up(x):
-    return None if x is None else torch.from_numpy(np.ascontiguousarray(x)).to(_dev())
-
-
-def _ratio(tag, case, got, ref, bound):
-    """Largest |got - ref| / bound; a zero bound admits only an exact match."""
-    err = np.abs(np.asarray(got, dtype=np.float64) - ref)
-    r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, np.inf))
-    worst = float(r.max())
-    print(f"RATIO {tag} {_id(case)} {worst:.4g}")
-    return worst
-
-
-def _lib():
-    from diffsound_amd import _hip
-
-    return _hip, _hip.lib()
 
 
 # ------------------------------------------------------------------------------------------ time-varying pair

@@ -35,34 +35,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _stft_ref as R  # noqa: E402
-from _guarded import Guarded, dev as _dev  # noqa: E402
+from _guarded import Guarded, _id, _lib, _ratio, _up, dev as _dev  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
 LOSS_CASES = [(c, k, a) for c in R.LOSS_SHAPES for k in (0, 1) for a in R.ALPHAS]
-
-
-def _id(case):
-    return "-".join(map(str, case))
-
-
-def _up(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).to(_dev())
-
-
-def _ratio(tag, case, got, ref, bound):
-    """Largest |got - ref| / bound; a zero bound admits only an exact match."""
-    err = np.abs(np.asarray(got, dtype=np.float64) - ref)
-    r = np.where(bound > 0, err / np.where(bound > 0, bound, 1.0), np.where(err == 0, 0.0, np.inf))
-    worst = float(r.max())
-    print(f"RATIO {tag} {_id(case)} {worst:.4g}")
-    return worst
-
-
-def _lib():
-    from diffsound_amd import _hip
-
-    return _hip, _hip.lib()
 
 
 # ------------------------------------------------------------------------------------------------------ STFT

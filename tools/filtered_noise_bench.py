@@ -9,7 +9,8 @@ Two workloads, forward + backward each:
            MSSLoss([512, 256, 128, 64, 32], l1_loss), backward, Adam step.
 ``--other`` names a second version of diffsound_amd/ddsp/oscillator.py (e.g. ``git show HEAD~1:diffsound_amd/ddsp/oscillator.py``
 saved to a file); it is loaded beside the package's own on the same library build - every kernel other than the noise branch is
-the same code - and the two are timed ALTERNATELY in one process.  Time: HIP events around ``--calls`` calls, per call, median
+the same code - and the two are timed ALTERNATELY in one process.  (A version from before the file was split is self-contained; a
+later one imports ``FilteredNoise`` from ddsp/filtered_noise.py, so name a version of that file's era.)  Time: HIP events around ``--calls`` calls, per call, median
 (min) over ``--rounds`` rounds after a warm-up.  Device activities: torch's kernel tracer on one call."""
 import argparse
 import importlib.util
