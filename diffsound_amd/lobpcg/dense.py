@@ -1,6 +1,9 @@
 """The small (<= 3b x 3b) dense algebra of the modal eigensolver - fp64, on the host - and the guard that keeps its LAPACK calls
 on one thread (lobpcg/modal_solver.py).  csrc/host_dense.cpp is its twin for the native loop: the functions there carry the same
-names without the underscore, and tests/test_cabi_cpu.py checks one against the other."""
+names without the underscore, and tests/test_cabi_cpu.py checks one against the other.  ``_gen_eigh`` - the generalised Ritz step
+of the fp64 polish and of the fp64 refinement (lobpcg/refine.py) - is the algebra ds_host_polish says there for the native
+polish; ``_basic_transform`` / ``_basic_ritz``, the Rayleigh-Ritz transform of ``ModalSolver.solve_basic``, have no twin: that
+iteration runs in the interpreter only."""
 import os
 import threading
 
@@ -14,6 +17,42 @@ def storage_eps(dtype):
 
 def _sym(G):
     return 0.5 * (G + G.transpose(0, 1))
+
+
+def _gen_eigh(GA, GB):
+    """(E, C) of the pencil (GA, GB), ascending, with C^T GB C = I: Cholesky factor of GB, its triangular inverse, ``eigh`` of the
+    transformed GA, back-transform.  Both are symmetrised first; a GB that is not positive definite raises LinAlgError."""
+    L = torch.linalg.cholesky(_sym(GB))
+    Li = torch.linalg.solve_triangular(L, torch.eye(L.shape[0], dtype=L.dtype), upper=False)
+    E, Zt = torch.linalg.eigh(_sym(Li @ _sym(GA) @ Li.transpose(0, 1)))
+    return E, (Li.transpose(0, 1) @ Zt).contiguous()
+
+
+def _basic_transform(GB, eps):
+    """Ri = D^-1/2 chol(D^-1/2 S^T B S D^-1/2)^-T of the reference's 'basic' method (``_get_rayleigh_ritz_transform``,
+    _lobpcg.py:479-525): None when the scaled Gram matrix has no Cholesky factor - or one so ill-conditioned that
+    S Ri would come out of the fp32 update visibly non-orthonormal (eps x cond(S^T B S) >= 1e-3: the vectors are stored with unit
+    roundoff ``eps``; the reference, which has no such test, then iterates on a basis that is no longer one).  A transform of its
+    own: ``_gen_eigh`` neither scales nor gates."""
+    GB = _sym(GB)
+    d = torch.rsqrt(torch.clamp(GB.diagonal(), min=1e-300))
+    L, info = torch.linalg.cholesky_ex(GB * d[:, None] * d[None, :])
+    if int(info) != 0 or not bool(torch.isfinite(L).all()):
+        return None
+    if eps / max(float(L.diagonal().min()), 1e-300) ** 2 >= 1e-3:
+        return None
+    Li = torch.linalg.solve_triangular(L, torch.eye(L.shape[0], dtype=L.dtype), upper=False)
+    return d[:, None] * Li.transpose(0, 1)
+
+
+def _basic_ritz(GA, GB, eps, keep=None):
+    """(Ritz values, the first ``keep`` columns of Ri Z) of the 'basic' method's step, or None without a transform."""
+    keep = GA.shape[0] if keep is None else keep
+    Ri = _basic_transform(GB, eps)
+    if Ri is None:
+        return None
+    E_, Z = torch.linalg.eigh(_sym(Ri.transpose(0, 1) @ _sym(GA) @ Ri))
+    return E_, (Ri @ Z[:, :keep]).contiguous()
 
 
 def _svqb_transform(G, tau=1e-12):

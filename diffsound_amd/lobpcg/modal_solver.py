@@ -18,7 +18,8 @@ implements, re-designed for MI355X:
     u^T K_lambda u, u^T K_mu u needed by the differentiable read-out.
 
 The module is split by concern: ``config.py`` (SolverConfig, tuned_config, ModalResult, SolverState), ``dense.py`` (the small
-host algebra and its one-thread guard), ``precond.py`` (the preconditioners); every name stays importable from here.
+host algebra and its one-thread guard), ``precond.py`` (the preconditioners), ``refine.py`` (the fp64 refinement behind
+``ModalSolver.refine64``, in named phases); every name stays importable from here.
 
 The ``ops`` protocol (``diffsound_amd/modal_ops.py``: the HIP implementation; ``oracle/ops_cpu.py``: the CPU stand-in).
 
@@ -49,10 +50,11 @@ from typing import Callable, Optional
 import torch
 
 from .config import ModalResult, SolverConfig, SolverState, tuned_config  # noqa: F401
-from .dense import (_one_thread, _orthonormal_columns, _orthonormalizer_q, _project_in_coefficients,  # noqa: F401
-                    _raw_basis_transform, _rr_step, _small, _svqb_transform, _sym, _thread_local_setters,
-                    one_blas_thread_for_this_thread, storage_eps)
+from .dense import (_basic_ritz, _gen_eigh, _one_thread, _orthonormal_columns, _orthonormalizer_q,  # noqa: F401
+                    _project_in_coefficients, _raw_basis_transform, _rr_step, _small, _svqb_transform, _sym,
+                    _thread_local_setters, one_blas_thread_for_this_thread, storage_eps)
 from .precond import ChebyshevBlockJacobi, TwoLevelChebyshev, _stats  # noqa: F401
+from .refine import refine64
 
 
 def _check_size(n, b, nrigid):
@@ -658,11 +660,11 @@ class ModalSolver:
         res = self._polish(X, k, it, rel[:k].clone(), history)
         res.coarse_iterations = self.nested_iterations
         if cfg.refine_tol > 0.0:
-            try:
-                res = self.refine64(res, k, float(A_norm), float(B_norm))
-            finally:  # (a step that raises must not leave the combined fp64 K array cached for a later material)
-                if hasattr(self.ops, "combined_k64"):
-                    self.ops.combined_k64(False)
+            res = self.refine64(res, k, float(A_norm), float(B_norm))
+            # (the refinement has released the combined fp64 K array itself, also when a step raised; this second release is the
+            # one the recorded call trace has after the read-out - tests/golden/solver_call_traces.json)
+            if hasattr(self.ops, "combined_k64"):
+                self.ops.combined_k64(False)
         return res
 
     # ------------------------------------------------------------------ the reference's "basic" method
@@ -692,28 +694,6 @@ class ModalSolver:
         tol = self._tolerance()
         eps = storage_eps(dt)
 
-        def transform(GB):
-            """Ri of the reference: None when the scaled Gram matrix has no Cholesky factor - or one so ill-conditioned that
-            S Ri would come out of the fp32 update visibly non-orthonormal (eps x cond(S^T B S) >= 1e-3: the vectors are stored in
-            ``dt``; the reference, which has no such test, then iterates on a basis that is no longer one)."""
-            GB = _sym(GB)
-            d = torch.rsqrt(torch.clamp(GB.diagonal(), min=1e-300))
-            L, info = torch.linalg.cholesky_ex(GB * d[:, None] * d[None, :])
-            if int(info) != 0 or not bool(torch.isfinite(L).all()):
-                return None
-            if eps / max(float(L.diagonal().min()), 1e-300) ** 2 >= 1e-3:
-                return None
-            Li = torch.linalg.solve_triangular(L, torch.eye(L.shape[0], dtype=L.dtype), upper=False)
-            return d[:, None] * Li.transpose(0, 1)
-
-        def ritz(GA, GB, keep=None):
-            keep = GA.shape[0] if keep is None else keep
-            Ri = transform(GB)
-            if Ri is None:
-                return None
-            E_, Z = torch.linalg.eigh(_sym(Ri.transpose(0, 1) @ _sym(GA) @ Ri))
-            return E_, (Ri @ Z[:, :keep]).contiguous()
-
         lam = torch.zeros(b, dtype=torch.float64, device=dev)
         rel = torch.full((b,), float("inf"), dtype=torch.float64, device=dev)
         nc, npc, ns = 0, 0, b  # converged leading columns, columns of P, columns of S in use
@@ -727,11 +707,11 @@ class ModalSolver:
             GA, GB = ops.gram(Sa, AS[:, :w], exact=True), ops.gram(Sa, BS[:, :w], exact=True)
             na = b - nc
             keep = na if it == 0 else min(w, 2 * na)
-            out = _small(lambda a_, b_, keep_=keep: ritz(a_, b_, keep_), dev, GA, GB)
+            out = _small(lambda a_, b_, keep_=keep: _basic_ritz(a_, b_, eps, keep_), dev, GA, GB)
             if out is None and npc:  # [X P W] numerically dependent: the step without P
                 idx = torch.cat([torch.arange(0, na, device=dev), torch.arange(na + npc, w, device=dev)])
                 keep = na
-                out = _small(lambda a_, b_, keep_=keep: ritz(a_, b_, keep_), dev, GA[idx][:, idx].contiguous(), GB[idx][:, idx].contiguous())
+                out = _small(lambda a_, b_, keep_=keep: _basic_ritz(a_, b_, eps, keep_), dev, GA[idx][:, idx].contiguous(), GB[idx][:, idx].contiguous())
                 if out is not None:
                     Zf = torch.zeros((w, keep), dtype=torch.float64, device=dev)
                     Zf[idx] = out[1]
@@ -773,200 +753,8 @@ class ModalSolver:
 
     # ------------------------------------------------------------------ fp64 refinement
     def refine64(self, res, k, A_norm, B_norm):
-        """Continue from the converged fp32 block with fp64 vectors (see SolverConfig.refine_tol): LOBPCG steps in
-        fp64.  One step = K W, M W for the new block (fp64 SpMM), one Rayleigh-Ritz on S = [Y | X | P | W] through the
-        generalised (3b + 6)-dimensional pencil (S^T K S, S^T M S) - the rigid modes come out as its six ~zero
-        eigenvalues and are dropped - and X, P and their products with K and M for the next step by linearity.
-        RAYLEIGH-RITZ BY RECURRENCE, as in the fp32 iteration: only the NEW columns meet the vectors - the Gram blocks
-        S^T K W and S^T M W (ONE pass over the rows of S, K W and M W per step: ds_gram64_blocks) - while the blocks among Y, X and P follow
-        from the last step's eigenvector matrix by (3b + 6)-dimensional algebra; every ``refine_refresh``-th step
-        recomputes all blocks from the vectors.  The n x b updates are ``ops.mix64`` (ds_mix64, fp64 MFMA) over the LIST
-        of blocks of S: one pass per result, no temporaries of the size of a block."""
-        ops, cfg = self.ops, self.cfg
-        dev = ops.device
-        X = res.block_vectors.double()
-        n, b = X.shape
-        Y = ops.rigid64()
-        ny = 0 if Y is None else 6
-        f64 = dict(dtype=torch.float64, device=dev)
-        KX, MX = torch.empty((n, b), **f64), torch.empty((n, b), **f64)
-        if hasattr(ops, "combined_k64"):
-            ops.combined_k64(True)  # one fp64 block array for K during the steps (released below)
-        ops.apply_K64(X, KX)
-        ops.apply_M64(X, MX)
-        if ny:
-            MY, KY = torch.empty_like(Y), torch.empty_like(Y)
-            ops.apply_M64(Y, MY)
-            ops.apply_K64(Y, KY)  # ~ eps ||K|| (the rigid modes are null vectors of K); kept, not assumed zero
-            Y6, KY6, MY6 = Y[:, :6], KY[:, :6], MY[:, :6]
-
-        def gen_eigh(GA_, GB_):
-            L = torch.linalg.cholesky(_sym(GB_))
-            Li = torch.linalg.solve_triangular(L, torch.eye(L.shape[0], dtype=L.dtype), upper=False)
-            E_, Zt = torch.linalg.eigh(_sym(Li @ _sym(GA_) @ Li.transpose(0, 1)))
-            return E_, (Li.transpose(0, 1) @ Zt).contiguous()
-
-        def full_grams(blocks, kblocks, mblocks):
-            # all pairs of blocks of S = [Y | X | P | W] against K S and M S: one pass over the rows each
-            return ops.gram_blocks(blocks, kblocks, symmetric=True), ops.gram_blocks(blocks, mblocks, symmetric=True)
-
-        # Rayleigh-Ritz on the fp32 block alone: the pairs whose residual is tested first, and an X that is
-        # K-diagonal / M-orthonormal - which every later step's X is by construction
-        GA, GB = ops.gram(X, KX), ops.gram(X, MX)
-        lam, C = _small(gen_eigh, dev, GA, GB)
-        X, KX, MX = ops.mix64([X], C), ops.mix64([KX], C), ops.mix64([MX], C)
-        P = KP = MP = None
-        # Every n-sized block of a step lives in a POOL of (n x b) buffers allocated once and used through column views (round 5):
-        # the number of active columns changes from step to step, and blocks of ever new sizes - 2 to 4.5 GB each at configs[4] -
-        # made the caching allocator release and re-request device memory in the middle of the steps (0.3 s of run-to-run spread)
-        pool = {}
-
-        def buf(name, cols, dtype=torch.float64):
-            t = pool.get(name)
-            if t is None:
-                t = pool[name] = torch.empty((n, b), dtype=dtype, device=dev)
-            return t[:, :cols]
-
-        G0A = G0B = None  # Gram blocks among [Y | X | P] of the current basis (fp64, m0 x m0), by recurrence
-        refresh = max(1, int(cfg.refine_refresh))
-        since = refresh  # the first step forms everything from the vectors
-        hist = []
-        for it in range(cfg.refine_maxit + 1):
-            fused64 = hasattr(ops, "residual64")  # (the HIP operators: norms in one pass, no fp64 residual block)
-            if fused64:
-                rn2, xn2 = ops.residual64(KX, MX, X, lam)
-                rn, R = torch.sqrt(rn2), None
-                rel = rn / (torch.sqrt(xn2) * (A_norm + lam.abs() * B_norm))
-            else:
-                R = torch.addcmul(KX, MX, lam[None, :], value=-1.0)
-                rn = torch.linalg.vector_norm(R, dim=0)
-                rel = rn / (torch.linalg.vector_norm(X, dim=0) * (A_norm + lam.abs() * B_norm))
-            worst = float(rel[:k].max())
-            hist.append(worst)
-            if worst < cfg.refine_tol or it == cfg.refine_maxit:
-                break
-            # soft locking: only the pairs that still miss the tolerance (with a margin) and the guard columns get a new
-            # search direction; the others stay in X and take part in every Rayleigh-Ritz step, nothing else
-            act = rel >= 0.3 * cfg.refine_tol
-            act[k:] = True
-            idx = torch.nonzero(act).reshape(-1)
-            if idx.numel() % 4:  # (the preconditioner's kernels take multiples of 4 columns)
-                rest_ = torch.nonzero(~act).reshape(-1)
-                pad = rest_[torch.argsort(rel[rest_], descending=True)[:4 - idx.numel() % 4]]
-                idx = torch.sort(torch.cat([idx, pad])).values
-            # W = B R in fp32 (columns scaled to unit norm: the preconditioner is linear), promoted to fp64
-            nact = int(idx.numel())
-            R32 = buf("R32", nact, torch.float32)
-            if fused64:
-                ops.residual64_scaled(KX, MX, lam, 1.0 / rn.clamp(min=1e-300), idx, out=R32)
-            else:
-                R32.copy_(R[:, idx] / rn[idx].clamp(min=1e-300)[None, :])
-            W32 = buf("W32", nact, torch.float32)
-            self.precond_apply(R32, W32)
-            for _ in range(max(0, int(cfg.refine_sweeps) - 1)):
-                # one more sweep of the preconditioned Richardson iteration: W <- W + B (R - K W), all fp32.  A step of
-                # the fp64 phase is dominated by its dense n x b products, not by the preconditioner: a stronger
-                # correction per step buys fewer steps
-                T32, D32 = buf("T32", nact, torch.float32), buf("D32", nact, torch.float32)
-                ops.apply_K(W32, T32)
-                torch.sub(R32, T32, out=T32)
-                self.precond_apply(T32, D32)
-                W32 += D32
-            W = buf("W", nact)
-            W.copy_(W32)
-            del R
-            KW, MW = buf("KW", nact), buf("MW", nact)
-            ops.apply_M64(W, MW)
-            ops.apply_K64(W, KW)
-            # (unit M-norm columns of W - a well scaled pencil - without touching the vectors: the scale wn comes off the
-            # diagonal of W^T M W below, goes into the small matrices there and into the coefficients of the update)
-            # pencil on S = [Y | X | P | W]  (P: the previous step's update directions - the locally optimal 3-term
-            # recurrence; without it the pairs next to the guard vectors crawl); should the Gram matrix of S be
-            # numerically singular (P and W nearly dependent close to convergence), the step is repeated without P
-            head = ([(Y6, KY6, MY6)] if ny else []) + [(X, KX, MX)] + ([(P, KP, MP)] if P is not None else [])
-            blocks = [h[0] for h in head] + [W]
-            offs = [0]
-            for blk in blocks:
-                offs.append(offs[-1] + blk.shape[1])
-            m, m0, na = offs[-1], offs[-2], W.shape[1]
-            if since >= refresh or G0A is None or G0A.shape[0] != m0:
-                GA, GB = full_grams(blocks, [h[1] for h in head] + [KW], [h[2] for h in head] + [MW])
-                wn = torch.rsqrt(torch.diagonal(GB)[m0:].clamp(min=1e-300))
-                for Gm in (GA, GB):
-                    Gm[:, m0:] *= wn[None, :]
-                    Gm[m0:, :] *= wn[:, None]
-                since = 1
-            else:  # only the new columns meet the vectors: S^T [K W | M W] in one pass over the rows
-                GA, GB = torch.zeros((m, m), **f64), torch.zeros((m, m), **f64)
-                GA[:m0, :m0], GB[:m0, :m0] = G0A, G0B
-                Gw = ops.gram_blocks(blocks, [KW, MW])
-                wn = torch.rsqrt(torch.diagonal(Gw[m0:, na:]).clamp(min=1e-300))
-                for Gm, G in ((GA, Gw[:, :na]), (GB, Gw[:, na:])):
-                    G = G * wn[None, :]
-                    G[m0:] *= wn[:, None]
-                    Gm[:, m0:] = G
-                    Gm[m0:, :m0] = G[:m0].transpose(0, 1)
-                since += 1
-            GA, GB = _sym(GA), _sym(GB)
-            use_p = P is not None
-            try:
-                E_, Z = _small(gen_eigh, dev, GA, GB)
-            except torch.linalg.LinAlgError:
-                if not use_p:
-                    raise
-                keep = torch.cat([torch.arange(0, offs[-3], device=dev), torch.arange(m0, m, device=dev)])  # without P
-                E_, Zk = _small(gen_eigh, dev, GA[keep][:, keep].contiguous(), GB[keep][:, keep].contiguous())
-                Z = torch.zeros((m, Zk.shape[1]), **f64)
-                Z[keep] = Zk
-            Zs = Z[:, ny:ny + b].contiguous()  # the six lowest pairs are the rigid modes
-            lam = E_[ny:ny + b].contiguous()
-            xo = ny  # row offset of X in S
-            # update directions: everything of the new X that is not the old X.  Their scale (unit M-norm) comes from the
-            # small algebra (Pn = S Zr), so the coefficients of the scaled directions in S are known before any n-sized
-            # work, and every result is ONE pass over the blocks of S (ds_mix64: each block read once, the result
-            # written once, no n x b temporaries)
-            Zr = Zs.clone()
-            Zr[xo:xo + b] = 0.0
-            pn2 = ((Zr.transpose(0, 1) @ GB) * Zr.transpose(0, 1)).sum(1)[idx].clamp(min=1e-300)
-            sc = torch.rsqrt(pn2)
-            Tp = (Zr[:, idx] * sc[None, :]).contiguous()
-            xi = 1 if ny else 0  # position of X in the head
-            Zu, Tu = Zs.clone(), Tp.clone()  # the same coefficients for the W held in memory (not scaled)
-            Zu[m0:] *= wn[:, None]
-            Tu[m0:] *= wn[:, None]
-            news = []
-            for which in range(3):  # the vectors, their K-products, their M-products
-                parts = [h[which] for h in head] + [(W, KW, MW)[which]]
-                # (two sets of pool buffers, alternating: a step reads the set the previous one wrote)
-                Xn = ops.mix64(parts, Zu, out=buf(f"X{which}_{it & 1}", b))
-                Pd = ops.mix64([(blk, offs[i_]) for i_, blk in enumerate(parts) if i_ != xi], Tu,
-                               out=buf(f"P{which}_{it & 1}", nact))  # (X's rows of Tu are zero)
-                news.append((Xn, Pd))
-            (X, P), (KX, KP), (MX, MP) = news
-            del news
-            # Gram blocks among [Y | X_new | P_new] for the next step: T^T G T with T the coefficients of that basis in S
-            T = torch.zeros((m, ny + b + idx.numel()), **f64)
-            if ny:
-                T[:ny, :ny] = torch.eye(ny, **f64)
-            T[:, ny:ny + b] = Zs
-            T[:, ny + b:] = Zr[:, idx] * sc[None, :]
-            G0A, G0B = _sym(T.transpose(0, 1) @ GA @ T), _sym(T.transpose(0, 1) @ GB @ T)
-            del W, KW, MW
-        if hasattr(ops, "combined_k64"):
-            ops.combined_k64(False)
-        U = X[:, :k].contiguous()
-        kparts = ops.apply_K64(U, torch.empty_like(U), terms=True)
-        MU = torch.empty_like(U)
-        ops.apply_M64(U, MU)
-        a = (U * kparts[0]).sum(0)
-        bq = (U * kparts[1]).sum(0) if len(kparts) > 1 else None
-        m_ = (U * MU).sum(0)
-        out = ModalResult(lam[:k].clone(), U, a, bq, m_, iterations=res.iterations, rerr=rel[:k].clone(),
-                          history=res.history, block_vectors=X)
-        out.coarse_iterations = res.coarse_iterations
-        out.refine_iterations = len(hist) - 1
-        out.refine_history = hist
-        return out
+        """Continue from the converged fp32 block with fp64 vectors (see SolverConfig.refine_tol): lobpcg/refine.py."""
+        return refine64(self, res, k, A_norm, B_norm)
 
     # ------------------------------------------------------------------ fp64 Rayleigh-Ritz polish
     def _polish(self, X, k, it, rerr, history):
@@ -979,12 +767,8 @@ class ModalSolver:
             # u^T K_i u, u^T M u of the wanted pairs.  (Until round 5 the quadratic forms were torch matmuls on the device: eight
             # more tiny launches per pass, and rocBLAS is free to sum a split-K product with atomics - the one place of a pass whose
             # last bits were not tied down; tests/test_fullsize_gpu.py compares two 8-lane runs bit for bit.)
-            GA_ = _sym(sum(c * G for c, G in zip(coef, GK_)))
             GB_ = _sym(GM_)
-            L = torch.linalg.cholesky(GB_)
-            Li = torch.linalg.solve_triangular(L, torch.eye(L.shape[0], dtype=L.dtype), upper=False)
-            E_, Zt = torch.linalg.eigh(_sym(Li @ GA_ @ Li.transpose(0, 1)))
-            C_ = (Li.transpose(0, 1) @ Zt).contiguous()  # generalized eigenvectors, C^T GB C = I
+            E_, C_ = _gen_eigh(_sym(sum(c * G for c, G in zip(coef, GK_))), GB_)  # generalized eigenvectors, C^T GB C = I
             Ck_ = C_[:, :k].contiguous()
             quad = lambda G: ((Ck_.transpose(0, 1) @ _sym(G)) * Ck_.transpose(0, 1)).sum(1)
             qs = torch.stack([quad(G) for G in GK_] + [quad(GB_)])

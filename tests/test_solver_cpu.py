@@ -320,8 +320,22 @@ def test_start_sweeps_are_ignored_without_a_nested_start(cube):
 # ---------------------------------------------------------------------------------------------------------------------
 # Call traces: which ``ops`` members a solve calls, in which order, on how many columns.  Recorded once
 # (tests/golden/solver_call_traces.json) and compared for equality: restructuring the solver's host code must not change what it
-# launches.  Every case is stopped by its tracker at step 3, so no trace depends on how many pairs have converged by then.
-_TRACED = ("apply_K", "apply_M", "apply_KM", "gram", "mix", "mix_inplace", "residual", "residual_fused")
+# launches.  The fp32 cases are stopped by their tracker at step 3, so no trace of theirs depends on how many pairs have converged
+# by then; the two refinement cases run their fp32 phase to convergence and three fp64 steps (the recording script watches their
+# margins).
+_TRACED = ("apply_K", "apply_M", "apply_KM", "gram", "mix", "mix_inplace", "residual", "residual_fused",
+           "apply_K64", "apply_M64", "gram_blocks", "mix64")  # (... and the fp64 refinement's)
+_TRACED_FUSED64 = ("residual64", "residual64_scaled", "combined_k64")
+
+
+def _columns(arg):
+    """What a trace entry says of one argument: a tensor's last dimension; of a LIST of blocks (mix64, gram_blocks) the number
+    of blocks and every block's columns - for a ``(block, first row)`` item the row too."""
+    if torch.is_tensor(arg):
+        return [int(arg.shape[-1])]
+    if isinstance(arg, (list, tuple)):
+        return [len(arg)] + [int(x) for blk in arg for x in ((blk[0].shape[1], blk[1]) if isinstance(blk, tuple) else blk.shape[1:])]
+    return []
 
 
 class _RecordingOps(CpuModalOps):
@@ -332,22 +346,41 @@ class _RecordingOps(CpuModalOps):
         self.log, self.level = log, level
 
 
-def _traced(name):
-    inner = getattr(CpuModalOps, name)
+class _RecordingOpsFused64(_RecordingOps):
+    """... offering the fp64 refinement's fused forms as plain torch stand-ins (the contracts of HipModalOps' members,
+    block_ops.py): the branches the solver takes on the device, traceable without one."""
+
+    def residual64(self, KX, MX, X, lam):
+        R = torch.addcmul(KX, MX, lam[None, :], value=-1.0)
+        return (R * R).sum(0), (X * X).sum(0)
+
+    def residual64_scaled(self, KX, MX, lam, scale, idx, out=None):
+        R = (KX[:, idx] - MX[:, idx] * lam[idx][None, :]) * scale[idx][None, :]
+        return R.float() if out is None else out.copy_(R)
+
+    def combined_k64(self, on):
+        pass  # (the HIP operators keep / release one combined fp64 K array: here only the call is recorded)
+
+
+def _traced(cls, name):
+    inner = getattr(cls, name)
 
     def call(self, *args, **kw):
-        self.log.append([self.level + name] + [int(t.shape[-1]) for t in args + tuple(kw.values()) if torch.is_tensor(t)])
+        flag = [int(a) for a in args if isinstance(a, bool)]  # (combined_k64's; the others' keyword flags are not in the record)
+        self.log.append([self.level + name] + [c for a in args + tuple(kw.values()) for c in _columns(a)] + flag)
         return inner(self, *args, **kw)
 
     return call
 
 
 for _name in _TRACED:
-    setattr(_RecordingOps, _name, _traced(_name))
+    setattr(_RecordingOps, _name, _traced(CpuModalOps, _name))
+for _name in _TRACED_FUSED64:
+    setattr(_RecordingOpsFused64, _name, _traced(_RecordingOpsFused64, _name))
 
 
-def _recording_ops(cube, log, two_level=False, fused=False):
-    """The cube's operators with every traced call logged.  ``two_level``: with a corner-node level that implements the WHOLE
+def _recording_ops(cube, log, two_level=False, fused=False, fused64=False):
+    """The cube's operators with every traced call logged.  ``fused64``: offering the refinement's fused forms.  ``two_level``: with a corner-node level that implements the WHOLE
     protocol (the Galerkin products P^T K P, P^T M P and the rigid basis of the corner nodes) - CpuModalOps' own coarse level
     serves the V-cycle only, and a nested start solves an eigenproblem on that level."""
     from oracle.ops_cpu import corner_embedding
@@ -355,7 +388,7 @@ def _recording_ops(cube, log, two_level=False, fused=False):
 
     args = (cube["Kl"], cube["Km"], cube["M3"], cube["v"], cube["lam"], cube["mu"])
     if not two_level:
-        ops = _RecordingOps(log, "", *args)
+        ops = (_RecordingOpsFused64 if fused64 else _RecordingOps)(log, "", *args)
     else:
         v, t = meshgen.kuhn_box(4)
         t2 = fem.to_high_order(torch.from_numpy(v), torch.from_numpy(t).long(), 2)[1].numpy()
@@ -366,6 +399,9 @@ def _recording_ops(cube, log, two_level=False, fused=False):
         ops.coarse.fused = fused
     ops.fused = fused
     return ops
+
+
+_REFINE3 = dict(lmax_cap=10.0, refine_tol=1e-10, refine_maxit=3, seed=4)  # (the seed: see make_solver_call_traces.py)
 
 
 def _call_traces(cube, monkeypatch, report=None):
@@ -391,14 +427,23 @@ def _call_traces(cube, monkeypatch, report=None):
         # ... and the same with the fused operators offered: the start block and the Ritz steps in coefficients
         "solve_fused": (dict(fused=True), dict(), "solve"),
         "solve_nested_two_level_fused": (dict(two_level=True, fused=True), dict(nested_tol=3e-3, start_sweeps=2), "solve"),
+        # the fp64 refinement behind a converged fp32 phase (no tracker), three steps: the pencil formed from the vectors on
+        # [Y X W], then twice by recurrence on [Y X P W] (the blocks among [Y X P] that a step leaves have the next step's shape, so
+        # P's arrival forces no refresh) - plain, and with the fused forms the HIP operators offer
+        "solve_refine": (dict(), _REFINE3, "solve"),
+        "solve_refine_fused": (dict(fused64=True), _REFINE3, "solve"),
     }
     traces = {}
     for case, (ops_kw, cfg_kw, method) in cases.items():
         ops = _recording_ops(cube, log, **ops_kw)
         solver = ModalSolver(ops, SolverConfig(block=24, **cfg_kw))
         del log[:]  # (the trace is the solve's: the constructor's power iterations are not part of it)
-        res = getattr(solver, method)(16, tracker=stop_at_3)
-        assert res.iterations == 3
+        if cfg_kw is _REFINE3:
+            res = solver.solve(16)
+            assert res.refine_iterations == 3
+        else:
+            res = getattr(solver, method)(16, tracker=stop_at_3)
+            assert res.iterations == 3
         traces[case] = [list(e) for e in log]
         if report is not None:
             report(case, solver)
@@ -407,8 +452,9 @@ def _call_traces(cube, monkeypatch, report=None):
 
 def test_call_traces_equal_the_recorded_ones(cube, monkeypatch):
     """The sequence of operator calls and preconditioner applications of ``solve`` (one-level; two-level with a nested start and
-    start sweeps; each also with the fused operators) and of ``solve_basic`` on the 4^3 ord-2 cube, k = 16, block = 24, against the
-    sequences recorded before the solver was split into phases (tests/golden/make_solver_call_traces.py)."""
+    start sweeps; each also with the fused operators), of ``solve_basic`` and of ``solve`` with three steps of the fp64 refinement
+    (plain, and with its fused forms) on the 4^3 ord-2 cube, k = 16, block = 24, against the sequences recorded before the solver -
+    and, later, the refinement - was split into phases (tests/golden/make_solver_call_traces.py)."""
     import json
     import os
 
@@ -418,3 +464,97 @@ def test_call_traces_equal_the_recorded_ones(cube, monkeypatch):
     assert sorted(got) == sorted(want)
     for case in want:
         assert got[case] == want[case], case
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The fp64 refinement's pure phases (diffsound_amd/lobpcg/refine.py) and the generalised Ritz step they share with the polish.
+def test_active_columns_keep_the_guards_and_pad_to_a_multiple_of_4_with_the_worst_of_the_rest():
+    from diffsound_amd.lobpcg.refine import active_columns
+
+    k, tol = 4, 1e-10
+    hi, lo = 1e-9, 1e-12  # misses / passes 0.3 * tol
+    # nothing wanted is active: the four guard columns are, whatever their own backward errors
+    rel = torch.tensor([lo, lo, lo, lo, lo, hi, lo, lo], dtype=torch.float64)
+    assert active_columns(rel.clone(), k, tol).tolist() == [4, 5, 6, 7]
+    # a count that is already a multiple of 4 is left alone: all eight
+    assert active_columns(torch.full((8,), hi, dtype=torch.float64), k, tol).tolist() == list(range(8))
+    # one wanted column + four guards = 5: padded to 8 with the three largest of the inactive, sorted
+    rel = torch.tensor([3e-12, hi, 1e-12, 2e-12, lo, lo, lo, lo], dtype=torch.float64)
+    assert active_columns(rel.clone(), k, tol).tolist() == list(range(8))
+    # (at b = 8 the three largest are all that is left.)  A case where the padding has to choose: k = 8 of b = 12, columns 1 and 5
+    # active + 4 guards = 6 -> 8 with the two worst of the six others, 3 (9e-12) and 6 (8e-12)
+    rel = torch.tensor([5e-12, hi, 1e-12, 9e-12, 2e-12, hi, 8e-12, 3e-12, lo, lo, lo, lo], dtype=torch.float64)
+    assert active_columns(rel.clone(), 8, tol).tolist() == [1, 3, 5, 6, 8, 9, 10, 11]
+
+
+def _spd_pencil(m, g):
+    """(GA, GB, E): GB SPD and well conditioned, GA with the generalised eigenvalues E = 1 ... m exactly separated by 1."""
+    A = torch.randn((m, m), generator=g, dtype=torch.float64)
+    GB = A @ A.T / m + torch.eye(m, dtype=torch.float64)
+    L = torch.linalg.cholesky(GB)
+    Q = torch.linalg.qr(torch.randn((m, m), generator=g, dtype=torch.float64)).Q
+    E = torch.arange(1, m + 1, dtype=torch.float64)
+    H = L @ Q
+    GA = H @ torch.diag(E) @ H.T
+    return 0.5 * (GA + GA.T), GB, E
+
+
+def test_ritz_pencil_with_p_equals_scipy():
+    """An SPD pencil on S = [Y (6) | X (8) | P (4) | W (4)] with eigenvalues 1 ... 22: rounding reaches the result as
+    eps x cond(GB) x |E| / gap, a few 1e-14 here, so 1e-12 holds for values and (sign-aligned) vectors alike."""
+    import scipy.linalg as sla
+
+    from diffsound_amd.lobpcg.refine import ritz_pencil
+
+    GA, GB, _ = _spd_pencil(22, torch.Generator().manual_seed(0))
+    E, Z = ritz_pencil(GA, GB, [0, 6, 14, 18, 22], True)
+    Er, Zr = sla.eigh(GA.numpy(), GB.numpy())
+    assert np.abs(E.numpy() - Er).max() < 1e-12 * np.abs(Er).max()
+    Zr = Zr * np.sign((Zr * Z.numpy()).sum(0))[None, :]
+    assert np.abs(Z.numpy() - Zr).max() < 1e-12
+
+
+def test_ritz_pencil_repeats_without_p_when_the_gram_matrix_is_singular():
+    """P duplicates W's columns: S^T M S = R^T R with R = the 18 x 18 Cholesky factor of [Y X W]'s Gram matrix and W's columns
+    once more.  R has small integer entries, so the factorisation runs in exact arithmetic and meets pivots that are exactly 0
+    at W: LinAlgError, whatever the LAPACK.  The fallback's eigenvalues are those of the pencil without P (1e-12) and its
+    coefficients have zero rows at P; without a P to drop the error stands."""
+    import scipy.linalg as sla
+
+    from diffsound_amd.lobpcg.refine import ritz_pencil
+
+    g = torch.Generator().manual_seed(1)
+    R0 = torch.triu(torch.randint(-1, 2, (18, 18), generator=g).double(), 1) + 4.0 * torch.eye(18, dtype=torch.float64)
+    cols = list(range(14)) + [14, 15, 16, 17] + [14, 15, 16, 17]  # [Y X | P = W | W]
+    R = R0[:, cols]
+    GB = R.T @ R
+    A0 = _spd_pencil(18, g)[0]
+    GA = A0[cols][:, cols]
+    offs = [0, 6, 14, 18, 22]
+    with pytest.raises(torch.linalg.LinAlgError):
+        torch.linalg.cholesky(GB)
+    E, Z = ritz_pencil(GA, GB, offs, True)
+    keep = list(range(14)) + list(range(18, 22))
+    Er = sla.eigh(GA[keep][:, keep].numpy(), GB[keep][:, keep].numpy(), eigvals_only=True)
+    assert E.shape == (18,) and Z.shape == (22, 18)
+    assert np.abs(E.numpy() - Er).max() < 1e-12 * np.abs(Er).max()
+    assert torch.equal(Z[14:18], torch.zeros((4, 18), dtype=torch.float64))
+    assert float((Z.T @ GB @ Z - torch.eye(18, dtype=torch.float64)).abs().max()) < 1e-12
+    # no P: offs names [Y | X | W] with the SAME singular matrix (W's last columns duplicated inside it)
+    with pytest.raises(torch.linalg.LinAlgError):
+        ritz_pencil(GA, GB, [0, 6, 18, 22], False)
+
+
+def test_gen_eigh_is_the_polish_algebra_bit_for_bit():
+    """``dense._gen_eigh`` against the lines ModalSolver._polish carried inline until the refinement moved to refine.py."""
+    from diffsound_amd.lobpcg.dense import _gen_eigh, _sym
+
+    GA_, GB_, _ = _spd_pencil(24, torch.Generator().manual_seed(2))
+    GA_, GB_ = _sym(GA_), _sym(GB_)  # (as _polish hands them over)
+    L = torch.linalg.cholesky(GB_)
+    Li = torch.linalg.solve_triangular(L, torch.eye(L.shape[0], dtype=L.dtype), upper=False)
+    E_, Zt = torch.linalg.eigh(_sym(Li @ GA_ @ Li.transpose(0, 1)))
+    C_ = (Li.transpose(0, 1) @ Zt).contiguous()
+    E, C = _gen_eigh(GA_, GB_)
+    assert torch.equal(E, E_) and torch.equal(C, C_)
+    assert float((C.T @ GB_ @ C - torch.eye(24, dtype=torch.float64)).abs().max()) < 1e-12
