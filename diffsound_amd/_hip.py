@@ -13,7 +13,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("DS_EXP_LIB") or os.path.join(_HERE, "csrc", "libdiffsound_hip.so")  # (DS_EXP_LIB: A/B builds, experiments)
-ABI_VERSION = 44  # DS_ABI_VERSION of include/diffsound_hip.h
+ABI_VERSION = 45  # DS_ABI_VERSION of include/diffsound_hip.h
 
 c_i32p = ctypes.POINTER(ctypes.c_int32)
 _P = ctypes.c_void_p
@@ -92,6 +92,8 @@ _SIGNATURES = {
     "ds_stft_power": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
     "ds_spec_loss": (_I, [_I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P]),
     "ds_stft_power_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "ds_spec_points_fwd": (_I, [_P, _I, _I, _I, _F, _I, _P, _I64, _I, _P, _P, _P, _P]),
+    "ds_spec_points_bwd": (_I, [_P, _P, _I, _I, _I, _P, _I64, _I, _P, _D, _P, _P]),
     "ds_bem_geometry": (_I, [_P, _I64, _P, _I64, _P, _P]),
     "ds_bem_assemble_workspace_bytes": (_I64, [_I64]),
     "ds_bem_assemble": (_I, [_P, _I64, _F, _P, _P, _I64, _P, _I64, _P, _P, _P]),

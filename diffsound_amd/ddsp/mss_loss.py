@@ -12,9 +12,11 @@ L1 on linear and log2 power, reference :50-62, 98-103, or the log RMSE, :118-122
 normalises both clips, turns their spectrograms into point clouds (``spec2point``, :19-48: the spectrogram VALUES are
 detached there, so the gradient reaches the prediction only through the mode positions ``freq``) and hands them to the
 third-party Sinkhorn solver ``geomloss.SamplesLoss("sinkhorn", p=2, blur=0.01)`` (``geomloss==0.2.6``,
-requirements.txt:46).  It stays on PyTorch: the spectrograms come from ``ds_stft_power``,
-the point clouds are torch ops, the solver is imported WHEN THE LOSS IS CALLED - constructing the module never needs
-the package, calling it without the package raises ImportError naming it.
+requirements.txt:46).  The spectrograms come from ``ds_stft_power``; the solver is imported WHEN THE LOSS IS CALLED -
+constructing the module never needs the package, calling it without the package raises ImportError naming it.  When the
+solver is this library's own (``ddsp/sinkhorn.py``, which ``compat/geomloss`` re-exports) the point clouds come from the
+kernels of csrc/specpoints.hip (``ddsp/spec_points.py``) and the target's clouds are kept between
+calls; with any other solver object they are the torch ops of ``spec2point``.
 Parity (round 5): values and gradients of the reference module itself - run in the build container with torchaudio's
 Spectrogram restated (torchaudio==2.0.2, absent from the image) - are the fixture G9; the kernels meet it to 2e-5
 (tests/test_mss_loss.py), beside the checks against oracle/mss_loss.py and torch.stft.
@@ -24,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from .. import _hip
+from .spec_points import spectral_points
 
 _KIND = {"l1_loss": 0, "rmse_loss": 1}
 _TYPES = ("l1_loss", "rmse_loss", "geomloss")
@@ -79,6 +82,11 @@ def _sinkhorn():
                           "(reference requirements.txt:46: geomloss==0.2.6), which is not installed; install it or "
                           "use type='l1_loss' / 'rmse_loss' (HIP kernels)") from e
     return SamplesLoss(loss="sinkhorn", p=2, blur=0.01)
+
+
+def _native_solver():
+    from .sinkhorn import SamplesLoss
+    return SamplesLoss
 
 
 def _as_clips(x):
@@ -152,6 +160,8 @@ class _SpecLoss(torch.autograd.Function):
 class SSSLoss(nn.Module):
     """Single-scale spectral loss (reference :70-122)."""
 
+    _fused_points = True  # False: the 'geomloss' clouds by the torch ops of spec2point also with the native solver (tests)
+
     def __init__(self, n_fft, sample_rate, alpha=1.0, overlap=0.75, eps=1e-7, type="geomloss"):
         super().__init__()
         if type not in _TYPES:
@@ -161,6 +171,7 @@ class SSSLoss(nn.Module):
         self.hop_length = int(n_fft * (1 - overlap))
         self.loss_type = type
         self.sample_rate = sample_rate
+        self._target_cache = None  # (x_true, its _version, scale, (lin, log)) of the last fused 'geomloss' call
 
     def spec(self, x):
         return stft_power(x, self.n_fft, self.hop_length)
@@ -180,14 +191,37 @@ class SSSLoss(nn.Module):
 
     def _forward_geomloss(self, x_pred, x_true, freq, scale):
         """Reference :104-117.  Spectrograms by ``ds_stft_power`` (their values carry no gradient here: spec2point
-        detaches them), point clouds in torch, Sinkhorn divergence by the third-party solver."""
+        detaches them).  With this library's own Sinkhorn solver (what ``compat/geomloss`` provides) the point clouds
+        come from ``ds_spec_points_fwd`` - both clouds of a clip in one call, the target's kept while the same target
+        tensor arrives unmodified, no host synchronisation in front of the solver; with any other solver object the
+        clouds are the torch ops of ``spec2point``."""
         if self.geomloss is None:
             self.geomloss = _sinkhorn()
+        if self._fused_points and isinstance(self.geomloss, _native_solver()):
+            return self._forward_geomloss_fused(x_pred, x_true, freq, scale)
         x_true, x_pred = normlize(_as_clips(x_true)), normlize(_as_clips(x_pred))
         lin_true, lin_pred = self.spec(x_true), self.spec(x_pred)
         log_true, log_pred = self.log_spec(x_true, scale) / 40, self.log_spec(x_pred, scale) / 40
         loss_lin = self.geomloss(spec2point(lin_pred, freq, self.sample_rate), spec2point(lin_true))
         loss_log = self.geomloss(spec2point(log_pred, freq, self.sample_rate), spec2point(log_true))
+        return self.alpha * loss_log + loss_lin
+
+    def _target_points(self, x_true, scale):
+        """The target's two clouds; rebuilt when another tensor object arrives, or the same one after an in-place
+        change (its ``_version``), or another ``scale``.  The key is the object, not its ``data_ptr``: the entry holds
+        the tensor, so its identity cannot pass to another one."""
+        key = self._target_cache
+        if key is not None and key[0] is x_true and key[1] == x_true._version and key[2] == scale:
+            return key[3]
+        clouds = spectral_points(self.spec(normlize(_as_clips(x_true))), None, None, scale, self.eps)
+        self._target_cache = (x_true, x_true._version, scale, clouds)
+        return clouds
+
+    def _forward_geomloss_fused(self, x_pred, x_true, freq, scale):
+        lin_true, log_true = self._target_points(x_true, scale)
+        lin_pred, log_pred = spectral_points(self.spec(normlize(_as_clips(x_pred))), freq, self.sample_rate, scale, self.eps)
+        loss_lin = self.geomloss(lin_pred, lin_true)
+        loss_log = self.geomloss(log_pred, log_true)
         return self.alpha * loss_log + loss_lin
 
 

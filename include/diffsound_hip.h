@@ -41,7 +41,7 @@ enum { DS_OK = 0, DS_ERR_ARG = 1, DS_ERR_HIP = 2, DS_ERR_NOMEM = 3 };
 /* Thread-local text of the last error returned on this thread ("" if none). */
 const char* ds_last_error(void);
 /* Library ABI version (bumped on any signature change); ds_abi_version() returns the value the library was built with. */
-#define DS_ABI_VERSION 44
+#define DS_ABI_VERSION 45
 int ds_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------------
@@ -728,6 +728,32 @@ int ds_spec_loss(int kind, const float* Pp, const float* Pt, int B, int F, int T
                  double* sums, float* gP, ds_stream_t stream);
 int ds_stft_power_bwd(const float* gP, const float* re, const float* im, int B, int S, int n_fft, int hop,
                       float gscale, float* gframes, float* gx, ds_stream_t stream);
+
+/* Point clouds of the early-phase spectral loss (ABI 45; reference src/ddsp/mss_loss.py:19-48, 104-117: spec2point on the
+ * 'geomloss' path).  From one power spectrogram P (B x F x T) f32, as ds_stft_power leaves it, both clouds of a scale:
+ * lin (B x F x 4) and log (B x fclip x 4), 1 <= fclip <= F.  Columns 0..2: F.interpolate(row, size=3, mode='linear',
+ * align_corners=False) of P (lin) or of (log2(P + eps) - log2(eps)) / 40 (log; the logarithm before the interpolation, no log
+ * spectrogram is written).  Column 3: row / bins, bins = the cloud's rows (F or fclip); with freq (E entries, f32, Hz) the
+ * reference's writes on top, in its order - rounds w = 2, 1, 0, cur = pos - w then cur = pos + w, pos = bins /
+ * (sample_rate // 2) * freq[e], cur / bins into row trunc(cur) of every batch when 0 <= trunc(cur) < bins; a later write
+ * overrides an earlier one, inside one write the highest e wins (a sequential index_put), non-finite entries write nothing.
+ * The position arithmetic is the fp32 operations torch performs on device tensors, correctly rounded, uncontracted; "/ bins" is
+ * the product with 1.0f / bins, torch's device form of a division by a scalar (csrc/specpoints.hip).
+ *   ds_spec_points_fwd  freq, win both NULL (target clouds: column 3 = row / bins) or both given; win: F + fclip 64-bit words
+ *                       (lin rows, then log rows), written here: 0 or (write + 1) << 56 | e of the row's winner.
+ *   ds_spec_points_bwd  g_freq[e] = gscale * sum over both clouds of (bins / (sample_rate // 2)) / bins * sum over the writes q of
+ *                       e whose row belongs to write q (of this or of another entry: autograd's rule for index_put_) of
+ *                       sum_b g[b, row, 3]; g_lin (B x F x 4), g_log (B x fclip x 4), either may be NULL (zero); gscale: the
+ *                       number of equal copies one entry stands for (1 for a dense list).
+ *                       freq, win: those of the forward.  A gather, batches ascending, fp64 sums: the same bits on every call.
+ *                       Nothing flows to P (the reference detaches it).
+ * Asynchronous on the stream, no allocation, no synchronisation.  Refused (DS_ERR_ARG, message in ds_last_error()): a null
+ * required pointer, B, F or T < 1, fclip outside [1, F], eps <= 0, E outside [1, 2^56), sample_rate < 2, clouds not 16-byte
+ * aligned. */
+int ds_spec_points_fwd(const float* P, int B, int F, int T, float eps, int fclip, const float* freq /*or NULL*/, int64_t E,
+                       int sample_rate, unsigned long long* win /*or NULL*/, float* lin, float* log, ds_stream_t stream);
+int ds_spec_points_bwd(const float* g_lin /*or NULL*/, const float* g_log /*or NULL*/, int B, int F, int fclip, const float* freq,
+                       int64_t E, int sample_rate, const unsigned long long* win, double gscale, float* g_freq, ds_stream_t stream);
 
 /* Launch timing hook for the benchmark's live roofline figure: while `stream` is registered (capacity > 0; 0 or a
  * NULL stream un-registers), every fused Chebyshev-term launch (ds_spmm_union epilogue 1) issued on it - from Python or
