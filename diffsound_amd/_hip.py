@@ -119,6 +119,8 @@ _SIGNATURES = {
     "ds_combine_tangent": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     "ds_tangent_forms_workspace_bytes": (ctypes.c_size_t, [_I64, _I]),
     "ds_tangent_forms": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _P, _P, ctypes.c_size_t, _P]),
+    "ds_mode_sample_fwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P]),
+    "ds_mode_sample_bwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P, _P]),
 }
 
 

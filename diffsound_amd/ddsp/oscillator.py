@@ -132,6 +132,19 @@ class _BankBase(nn.Module):
         a = None if amp is None else amp.reshape(self.audio_num, self.mode_num).to(dev)
         return oscillator_bank(d, w, a, force, self.sample_num, self.sr)
 
+    def _with_gain(self, amp, mode_gain):
+        """``amp`` (A, m, 1) or None (unit amplitudes) times ``mode_gain`` (audio_num, mode_num): the gains of a strike
+        (``diffsound_amd.impact.ContactSurface.amplitudes``) in place of, or on top of, the free amplitudes.  None
+        returns ``amp`` itself - the path and the bits of a call without the keyword."""
+        if mode_gain is None:
+            return amp
+        if not torch.is_tensor(mode_gain) or tuple(mode_gain.shape) != (self.audio_num, self.mode_num):
+            raise ValueError(f"mode_gain must be a ({self.audio_num}, {self.mode_num}) tensor, got "
+                             f"{tuple(mode_gain.shape) if torch.is_tensor(mode_gain) else type(mode_gain).__name__}")
+        if amp is None:
+            return mode_gain.float().reshape(self.audio_num, self.mode_num, 1)
+        return amp * mode_gain.to(amp.device, amp.dtype).reshape(self.audio_num, self.mode_num, 1)
+
 
 class TraditionalDampedOscillator(_BankBase):
     """Fixed Rayleigh damping (alpha, beta from the material), unit amplitudes
@@ -143,8 +156,8 @@ class TraditionalDampedOscillator(_BankBase):
         self.alpha = mat.alpha
         self.beta = mat.beta
 
-    def forward(self, freq_linear):
-        sig = self._render(freq_linear, float(self.alpha), float(self.beta), None)
+    def forward(self, freq_linear, mode_gain=None):
+        sig = self._render(freq_linear, float(self.alpha), float(self.beta), self._with_gain(None, mode_gain))
         w = self.damped_freq[0, :, 0].double() * (2 * np.pi)
         self.undamped_freq = freq_linear.reshape(1, self.mode_num, 1).to(w.device)
         return sig
@@ -166,8 +179,8 @@ class DampedOscillator(_BankBase):
         # unused by forward(), kept so that the reference's checkpoints load strictly (oscillator.py:78: "just for load")
         self.noise = FilteredNoise(audio_num, 8000)
 
-    def forward(self, freq_linear, non_linear_rate=0.0, noise_rate=0.0):
-        return self._render(freq_linear, self.alpha(), self.beta(), self.amp())
+    def forward(self, freq_linear, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None):
+        return self._render(freq_linear, self.alpha(), self.beta(), self._with_gain(self.amp(), mode_gain))
 
     def _curve_render(self, freq_linear, damping_curve):
         dev, force = self._force_on_device()
@@ -255,11 +268,11 @@ class GTDampedOscillator(_BankBase):
         lbd = (self.freq_linear() * 2 * np.pi) ** 2
         return 0.5 * (self.alpha() + self.beta() * lbd)
 
-    def forward(self, non_linear_rate=0.0, noise_rate=0.0):
+    def forward(self, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None):
         if non_linear_rate != 0.0:
-            sig = self._render_time_varying(non_linear_rate)
+            sig = self._render_time_varying(non_linear_rate, mode_gain)
         else:
-            sig = self._render(self.freq_linear(), self.alpha(), self.beta(), self.amp())
+            sig = self._render(self.freq_linear(), self.alpha(), self.beta(), self._with_gain(self.amp(), mode_gain))
             fd = self.damped_freq[0, :, 0].double()
             d = self.damping().reshape(-1).double().to(fd.device)
             self.undamped_freq = (torch.sqrt((2 * np.pi * fd) ** 2 + d ** 2) / (2 * np.pi)).float().reshape(1, -1, 1)
@@ -267,7 +280,7 @@ class GTDampedOscillator(_BankBase):
             sig = sig + self.noise() * noise_rate
         return sig
 
-    def _render_time_varying(self, rate):
+    def _render_time_varying(self, rate, mode_gain=None):
         """reference :219-242 with the (A, m, S) cumsum / exp / sin / mode-sum / conv1d chain as one kernel pair."""
         if self.force_frame_num > FIR_MAX_FORCE:
             raise ValueError(f"time-varying render (non_linear_rate != 0): force of {self.force_frame_num} taps, the FIR "
@@ -279,5 +292,5 @@ class GTDampedOscillator(_BankBase):
         damp = 0.5 * (self.alpha().to(dev) + self.beta().to(dev) * lbd)
         freq = (lbd - damp ** 2) ** 0.5 / (2 * np.pi)
         self.undamped_freq = ((2 * np.pi * freq) ** 2 + damp ** 2) ** 0.5 / (2 * np.pi)
-        amp = self.amp().reshape(self.audio_num, self.mode_num).to(dev)
+        amp = self._with_gain(self.amp(), mode_gain).reshape(self.audio_num, self.mode_num).to(dev)
         return oscillator_bank_tv(damp, freq, amp, force.detach(), self.sample_num, self.sr)

@@ -990,6 +990,30 @@ size_t ds_tangent_forms_workspace_bytes(int64_t nv, int m);
 int ds_tangent_forms(const int32_t* rowptr, const int32_t* colidx, const double* klam, int64_t nv, const float* U,
                      int64_t ldu, int m, double* Q, void* work, size_t work_bytes, ds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Mode shapes sampled at points of the mesh: the modal gains of a strike (csrc/modesample.hip).  Stands in for the free
+ * ``amp`` of the reference's oscillator modules (src/ddsp/oscillator.py:76), which nothing ties to the mode shapes: a
+ * strike at point p with direction d excites mode i with the gain d . u_i(p).
+ *
+ * Common arguments: tets (T x N) int32, N = 4 (order 1) or 10 (order 2), local node order of fem_tables.py; U (3 nv x m)
+ * fp64, row 3 * node + c, leading dimension ldu >= m (the layout of DiffSoundObj.U_hat); per point p of P: elem[p]
+ * int32 element id, L[p] four fp32 barycentrics of that element, dir[p] three fp32 components.  Element ids and node
+ * ids are the caller's to check (as for the Deform operators above).  fp64 buffers 8-byte aligned.  Asynchronous on
+ * the stream; nothing is allocated.  One wave owns a point and sums in a fixed order: two calls give the same bits.
+ * There is no gradient to U: the eigenvectors are constants.
+ * ---------------------------------------------------------------------------------------------- */
+/* out[p, i] = sum_a N_a(L_p) sum_c dir[p, c] U[3 tets[elem_p, a] + c, i]   (P x m fp64), the shape functions in fp64
+ * from the fp32 L; vec[p, i, c] = sum_a N_a U[3 node_a + c, i] (P x m x 3 fp64), the displacement without the dot
+ * product.  Either output may be NULL, not both; dir may be NULL when out is. */
+int ds_mode_sample_fwd(const int32_t* tets, int64_t T, int N, int64_t nv, const double* U, int64_t ldu, int m,
+                       const int32_t* elem, const float* L, const float* dir, int64_t P, double* out, double* vec,
+                       ds_stream_t stream);
+/* gout (P x m) fp64 ->  gL[p, j] = sum_i gout[p, i] sum_a dN_a/dL_j dir_p . U[node_a, :, i]   (P x 4 fp64)  and
+ * gdir[p, c] = sum_i gout[p, i] sum_a N_a U[3 node_a + c, i]   (P x 3 fp64).  Either may be NULL, not both. */
+int ds_mode_sample_bwd(const int32_t* tets, int64_t T, int N, int64_t nv, const double* U, int64_t ldu, int m,
+                       const int32_t* elem, const float* L, const float* dir, int64_t P, const double* gout, double* gL,
+                       double* gdir, ds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
