@@ -22,112 +22,12 @@ _I = ctypes.c_int
 _D = ctypes.c_double
 _F = ctypes.c_float
 
-_SIGNATURES = {
-    "ds_last_error": (ctypes.c_char_p, []),
-    "ds_abi_version": (_I, []),
-    "ds_pattern_build": (_I, [_P, _I64, _I, _I64, _I, ctypes.POINTER(_P)]),
-    "ds_pattern_sizes": (_I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
-    "ds_pattern_export": (_I, [_P, _P, _P, _P, _P, _P]),
-    "ds_pattern_free": (None, [_P]),
-    "ds_dpattern_build": (_I, [_P, _I64, _I, _I64, _I, _P, ctypes.POINTER(_P)]),
-    "ds_dpattern_sizes": (_I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64),
-                               ctypes.POINTER(_I64)]),
-    "ds_dpattern_export": (_I, [_P] * 13),
-    "ds_dpattern_free": (None, [_P]),
-    "ds_spmm_f64_polish": (_I, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _P]),
-    "ds_spmm_f64_union": (_I, [_I, _I, _P, _P, _I64, _I, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _P]),
-    "ds_spmm_f64_polish_f32out": (_I, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _P]),
-    "ds_pack_kc": (_I, [_P, _P, _I64, _P, _P]),
-    "ds_spmm_union16m": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _I64, _P, _I64, _P, _I64, _I, _P, _I64, _P, _I, _F,
-                              _F, _I, _P, _I64, _P]),
-    "ds_spmm_union32m": (_I, [_I, _I, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _I64, _P, _I64, _P, _I64, _I, _P]),
-    "ds_edge_table": (_I, [_P, _I64, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
-    "ds_unique_rows3": (_I, [_P, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
-    "ds_assemble_kml": (_I, [_P, _P, _I64, _I, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
-    "ds_combine_material": (_I, [_P, _P, _P, _I64, _P, _I64, _D, _D, _P, _P, _P, _P, _P]),
-    "ds_spmm_bsr3": (_I, [_I, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I, _P]),
-    "ds_gram_workspace_bytes": (_I64, [_I64, _I, _I]),
-    "ds_gram": (_I, [_P, _I, _I64, _I, _P, _I, _I64, _I, _I64, _I, _P, _P, _I64, _P]),
-    "ds_residual": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _P]),
-    "ds_cheb_init": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _F, _P]),
-    "ds_cheb_step": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _F, _F, _P]),
-    "ds_cheb_spmm": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _F, _F, _I, _P]),
-    "ds_spmm_residual": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P]),
-    "ds_scalar_csr_spmm": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I, _F, _P]),
-    "ds_groups_build": (_I, [_P, _P, _I64, ctypes.POINTER(_P)]),
-    "ds_groups_sizes": (_I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
-    "ds_groups_export": (_I, [_P, _P, _P, _P, _P]),
-    "ds_groups_free": (None, [_P]),
-    "ds_pack_groups": (_I, [_P, _P, _I64, _P, _P]),
-    "ds_geometry_grad": (_I, [_P, _I64, _I, _I64, _P, _P, _I64, _I, _P, _P, _D, _D, _P, _P, _I, _P, _P, _P]),
-    "ds_spmm_union": (_I, [_I, _I, _P, _P, _I64, _I, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _F, _F, _I, _P,
-                          _I64, _P]),
-    "ds_union_residual_workspace_bytes": (_I64, [_I64, _I]),
-    "ds_spmm_union_narrow": (_I, [_I, _I, _P, _P, _I64, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _P]),
-    "ds_spmm_union_km": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P]),
-    "ds_union_residual": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _P, _I64, _I, _P, _I64, _P, _P, _P]),
-    "ds_union_residual_pre": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _P, _F, _P, _I64, _P, _I64, _I, _P,
-                                   _I64, _P, _P, _P]),
-    "ds_mix": (_I, [_P, _I64, _I, _P, _I, _P, _I64, _I64, _F, _F, _P]),
-    "ds_gram64_blocks": (_I, [_I, _P, _I, _P, _I64, _I, _P, _P, _I64, _P]),
-    "ds_residual64_workspace_doubles": (_I64, [_I]),
-    "ds_residual64_norms": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P, _I64, _P, _P, _P]),
-    "ds_residual64_scaled": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _I, _P, _I64, _I64, _P]),
-    "ds_mix64": (_I, [_I, _P, _P, _I64, _I, _P, _I64, _I64, _D, _D, _P]),
-    "ds_osc_bank_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),
-    "ds_osc_bank_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
-    "ds_readout_pass": (_I, [_P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _D, _D, _D, _P, _I, _I, _D, _P, _I, _P, _P, _P, _P, _P, _P]),
-    "ds_osc_tv_workspace_floats": (_I64, [_I, _I, _I]),
-    "ds_osc_tv_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P]),
-    "ds_osc_tv_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
-    "ds_osc_driven_workspace_bytes": (_I64, [_I, _I, _I]),
-    "ds_osc_driven_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
-    "ds_osc_driven_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P]),
-    "ds_filtered_noise_fwd": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _P]),
-    "ds_filtered_noise_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),
-    "ds_stream_triad": (_I, [_P, _P, _P, _I64, _F, _P]),
-    "ds_profile_stream": (_I, [_P, _I64]),
-    "ds_profile_collect": (_I64, [_P, _P, _P, _P, _P, _I64]),
-    "ds_profile_kinds": (_I, [ctypes.c_uint]),
-    "ds_stft_power": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
-    "ds_spec_loss": (_I, [_I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P]),
-    "ds_stft_power_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
-    "ds_spec_points_fwd": (_I, [_P, _I, _I, _I, _F, _I, _P, _I64, _I, _P, _P, _P, _P]),
-    "ds_spec_points_bwd": (_I, [_P, _P, _I, _I, _I, _P, _I64, _I, _P, _D, _P, _P]),
-    "ds_bem_geometry": (_I, [_P, _I64, _P, _I64, _P, _P]),
-    "ds_bem_assemble_workspace_bytes": (_I64, [_I64]),
-    "ds_bem_assemble": (_I, [_P, _I64, _F, _P, _P, _I64, _P, _I64, _P, _P, _P]),
-    "ds_bem_cgemv": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
-    "ds_bem_potential": (_I, [_P, _I64, _F, _P, _P, _P, _I64, _P, _P]),
-    "ds_mt_count_workspace_bytes": (_I64, [_I64, _I64, _I64]),
-    "ds_mt_count": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
-    "ds_mt_emit": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    "ds_mt_backward_workspace_floats": (_I64, [_I64]),
-    "ds_mt_backward": (_I, [_P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P]),
-    "ds_mesh_sdf_pack": (_I, [_P, _P, _I64, _I64, _P, _P]),
-    "ds_mesh_sdf_workspace_bytes": (_I64, [_I64, _I64, _I]),
-    "ds_mesh_sdf_query": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _P]),
-    "ds_sinkhorn_workspace_floats": (_I64, [_I64, _I64, _I64]),
-    "ds_sinkhorn_bbox": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
-    "ds_sinkhorn_loop": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _I, _I, _P, _P]),
-    "ds_sinkhorn_final": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P]),
-    "ds_sinkhorn_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P, _P, _P]),
-    "ds_deform_tables": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _P, _P, _P]),
-    "ds_deform_gradient": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _I64, _I, _P, _P]),
-    "ds_deform_force": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P]),
-    "ds_geometry_grad_tangent": (_I, [_P, _I64, _I, _I64, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
-    "ds_combine_tangent": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
-    "ds_tangent_forms_workspace_bytes": (ctypes.c_size_t, [_I64, _I]),
-    "ds_tangent_forms": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _P, _P, ctypes.c_size_t, _P]),
-    "ds_mode_sample_fwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P]),
-    "ds_mode_sample_bwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P, _P]),
-}
-
 
 class MtCounts(ctypes.Structure):
     """ds_mt_counts_t of include/diffsound_hip.h."""
     _fields_ = [("n_used", _I64), ("n_cross", _I64), ("n_side1", _I64), ("n_side3", _I64), ("n_inner", _I64),
                 ("n_face1", _I64), ("n_face2", _I64), ("reserved", _I64)]
+
 
 class Block64(ctypes.Structure):
     """ds_block64_t of include/diffsound_hip.h."""
@@ -176,6 +76,200 @@ class LobpcgDesc(ctypes.Structure):
                 ("res_work", _P), ("res_work_bytes", _I64), ("gram_work", _P), ("gram_work_bytes", _I64), ("lam", ctypes.POINTER(_D)), ("rerr", ctypes.POINTER(_D)),
                 ("history", ctypes.POINTER(_D)), ("history_cap", _i32), ("iterations", _i32), ("result_in_s2", _i32),
                 ("wait_mode", _i32), ("ritz_tol", ctypes.c_double)]
+
+
+_LEVEL, _TWOLEVEL, _LOBPCG, _LAPACK = (ctypes.POINTER(t) for t in (LevelDesc, TwoLevelDesc, LobpcgDesc, LapackTable))
+
+# Every entry point of the header, by translation unit in the header's order: (result, arguments).  A new one goes HERE.
+_SIGNATURES = {
+    "ds_last_error": (ctypes.c_char_p, []),
+    "ds_abi_version": (_I, []),
+    # symbolic phase: pattern.cpp (host), dpattern.hip (device)
+    "ds_pattern_build": (_I, [_P, _I64, _I, _I64, _I, ctypes.POINTER(_P)]),
+    "ds_pattern_sizes": (_I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "ds_pattern_export": (_I, [_P, _P, _P, _P, _P, _P]),
+    "ds_pattern_free": (None, [_P]),
+    "ds_groups_build": (_I, [_P, _P, _I64, ctypes.POINTER(_P)]),
+    "ds_groups_sizes": (_I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64)]),
+    "ds_groups_export": (_I, [_P, _P, _P, _P, _P]),
+    "ds_groups_free": (None, [_P]),
+    "ds_dpattern_build": (_I, [_P, _I64, _I, _I64, _I, _P, ctypes.POINTER(_P)]),
+    "ds_dpattern_sizes": (_I, [_P, ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64), ctypes.POINTER(_I64),
+                               ctypes.POINTER(_I64)]),
+    "ds_dpattern_export": (_I, [_P] * 13),
+    "ds_dpattern_free": (None, [_P]),
+    "ds_edge_table": (_I, [_P, _I64, _I64, _P, _P, _P, ctypes.POINTER(_I64), _P]),
+    "ds_unique_rows3": (_I, [_P, _I64, _P, _P, ctypes.POINTER(_I64), _P]),
+    # numeric assembly: assemble.hip
+    "ds_assemble_kml": (_I, [_P, _P, _I64, _I, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "ds_combine_material": (_I, [_P, _P, _P, _I64, _P, _I64, _D, _D, _P, _P, _P, _P, _P]),
+    # block SpMM: spmm.hip
+    "ds_spmm_bsr3": (_I, [_I, _P, _P, _P, _P, _I64, _P, _I64, _P, _I64, _I, _P]),
+    # tall-skinny Gram: gram.hip
+    "ds_gram_workspace_bytes": (_I64, [_I64, _I, _I]),
+    "ds_gram": (_I, [_P, _I, _I64, _I, _P, _I, _I64, _I, _I64, _I, _P, _P, _I64, _P]),
+    # fused block-vector updates: blockops.hip, spmm.hip, transfer.hip, spmm_f64.hip, spmm_union.hip
+    "ds_residual": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P, _P, _P]),
+    "ds_cheb_init": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _F, _P]),
+    "ds_cheb_step": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _F, _F, _P]),
+    "ds_cheb_spmm": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _F, _F, _I, _P]),
+    "ds_spmm_residual": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P]),
+    "ds_scalar_csr_spmm": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I, _F, _P]),
+    "ds_spmm_f64_polish": (_I, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _P]),
+    "ds_spmm_f64_union": (_I, [_I, _I, _P, _P, _I64, _I, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _P]),
+    "ds_spmm_f64_polish_f32out": (_I, [_P, _P, _P, _P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _P]),
+    "ds_pack_groups": (_I, [_P, _P, _I64, _P, _P]),
+    "ds_spmm_union": (_I, [_I, _I, _P, _P, _I64, _I, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _P, _I, _F, _F, _I, _P,
+                          _I64, _P]),
+    "ds_union_residual_workspace_bytes": (_I64, [_I64, _I]),
+    "ds_union_residual": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _P, _I64, _I, _P, _I64, _P, _P, _P]),
+    "ds_union_residual_pre": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _P, _F, _P, _I64, _P, _I64, _I, _P,
+                                   _I64, _P, _P, _P]),
+    "ds_spmm_union_narrow": (_I, [_I, _I, _P, _P, _I64, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _P]),
+    "ds_spmm_union_km": (_I, [_I, _P, _P, _I64, _I, _P, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P]),
+    # two-level cycle and its bf16 kernels: vcycle.cpp, spmm_union.hip, spmm_mfma.hip, spmm_mfma32.hip, precond16.hip
+    "ds_twolevel_apply": (_I, [_TWOLEVEL, _P]),
+    "ds_chebyshev_apply": (_I, [_LEVEL, _P, _I64, _P, _I64, _P, _P, _I64, _I, _P]),
+    "ds_chebyshev_apply16": (_I, [_LEVEL, _P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _P]),
+    "ds_spmm_union16": (_I, [_I, _P, _P, _I64, _I, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _P, _I64, _P, _I, _F,
+                            _F, _I, _P, _I64, _P]),
+    "ds_pack_kc": (_I, [_P, _P, _I64, _P, _P]),
+    "ds_group_inverse": (_I, [_P, _P, _P, _I64, _I, _P, _P]),
+    "ds_group_pack_kc": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _P, _P]),
+    "ds_group_apply16": (_I, [_P, _I, _P, _I, _I64, _P, _I, _I64, _I64, _I, _P]),
+    "ds_spmm_union16m": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I64, _I64, _I, _I, _I64, _P, _I64, _P, _I64, _I, _P, _I64, _P, _I, _F,
+                              _F, _I, _P, _I64, _P]),
+    "ds_spmm_union32m": (_I, [_I, _I, _P, _P, _P, _P, _P, _I64, _I64, _I64, _I, _I, _I64, _P, _I64, _P, _I64, _I, _P]),
+    "ds_cheb_init16": (_I, [_P, _I, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _F, _P]),
+    "ds_scalar_csr_spmm16": (_I, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I, _F, _P]),
+    # the native iteration and its steps: lobpcg.cpp, host_dense.cpp, blockops.hip, refine64.hip, gram.hip, mix64.hip
+    "ds_lobpcg_iterate": (_I, [_LOBPCG, _LAPACK, _P]),
+    "ds_selftest_dense": (_I, [_LAPACK, _I, _I, ctypes.c_uint, ctypes.POINTER(_D)]),
+    "ds_host_start_block": (_I, [_LAPACK, _P, _I, _I, _D, _D, _P, _P, _P, ctypes.POINTER(_D), ctypes.POINTER(_I)]),
+    "ds_host_polish": (_I, [_LAPACK, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
+    "ds_host_raw_basis": (_I, [_LAPACK, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, ctypes.POINTER(_I)]),
+    "ds_host_rr_step": (_I, [_LAPACK, _P, _I, _I, _P, _P, _P]),
+    "ds_host_wait_mode": (_I, [_I]),
+    "ds_mix": (_I, [_P, _I64, _I, _P, _I, _P, _I64, _I64, _F, _F, _P]),
+    "ds_residual64_workspace_doubles": (_I64, [_I]),
+    "ds_residual64_norms": (_I, [_P, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _P, _I64, _P, _P, _P]),
+    "ds_residual64_scaled": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _I, _P, _I64, _I64, _P]),
+    "ds_gram64_blocks": (_I, [_I, _P, _I, _P, _I64, _I, _P, _P, _I64, _P]),
+    "ds_mix64": (_I, [_I, _P, _P, _I64, _I, _P, _I64, _I64, _D, _D, _P]),
+    # geometry backward: geomgrad.hip
+    "ds_geometry_grad": (_I, [_P, _I64, _I, _I64, _P, _P, _I64, _I, _P, _P, _D, _D, _P, _P, _I, _P, _P, _P]),
+    "ds_geometry_grad_tangent": (_I, [_P, _I64, _I, _I64, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
+    # oscillator family and the pass's read-out: oscillator.hip, readout.hip, osc_driven.hip, filtered_noise.hip
+    "ds_osc_bank_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),
+    "ds_osc_bank_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
+    "ds_readout_pass": (_I, [_P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _D, _D, _D, _P, _I, _I, _D, _P, _I, _P, _P, _P, _P, _P, _P]),
+    "ds_osc_tv_workspace_floats": (_I64, [_I, _I, _I]),
+    "ds_osc_tv_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P]),
+    "ds_osc_tv_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
+    "ds_osc_driven_workspace_bytes": (_I64, [_I, _I, _I]),
+    "ds_osc_driven_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
+    "ds_osc_driven_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P]),
+    "ds_filtered_noise_fwd": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _P]),
+    "ds_filtered_noise_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),
+    # spectral loss head: stft.hip, specpoints.hip
+    "ds_stft_power": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P]),
+    "ds_spec_loss": (_I, [_I, _P, _P, _I, _I, _I, _F, _F, _I, _P, _P, _P]),
+    "ds_stft_power_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P]),
+    "ds_spec_points_fwd": (_I, [_P, _I, _I, _I, _F, _I, _P, _I64, _I, _P, _P, _P, _P]),
+    "ds_spec_points_bwd": (_I, [_P, _P, _I, _I, _I, _P, _I64, _I, _P, _D, _P, _P]),
+    # kernel timing and the bandwidth probe: profile.cpp, stream.hip
+    "ds_profile_stream": (_I, [_P, _I64]),
+    "ds_profile_kinds": (_I, [ctypes.c_uint]),
+    "ds_profile_collect": (_I64, [_P, _P, _P, _P, _P, _I64]),
+    "ds_stream_triad": (_I, [_P, _P, _P, _I64, _F, _P]),
+    # boundary elements: bem.hip
+    "ds_bem_geometry": (_I, [_P, _I64, _P, _I64, _P, _P]),
+    "ds_bem_assemble_workspace_bytes": (_I64, [_I64]),
+    "ds_bem_assemble": (_I, [_P, _I64, _F, _P, _P, _I64, _P, _I64, _P, _P, _P]),
+    "ds_bem_cgemv": (_I, [_P, _I64, _P, _I64, _P, _P, _P]),
+    "ds_bem_potential": (_I, [_P, _I64, _F, _P, _P, _P, _I64, _P, _P]),
+    # marching tetrahedra: dmtet.hip
+    "ds_mt_count_workspace_bytes": (_I64, [_I64, _I64, _I64]),
+    "ds_mt_count": (_I, [_P, _I64, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _P, _P]),
+    "ds_mt_emit": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "ds_mt_backward_workspace_floats": (_I64, [_I64]),
+    "ds_mt_backward": (_I, [_P, _P, _P, _I64, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P, _P]),
+    # mesh signed distance: meshsdf.hip
+    "ds_mesh_sdf_pack": (_I, [_P, _P, _I64, _I64, _P, _P]),
+    "ds_mesh_sdf_workspace_bytes": (_I64, [_I64, _I64, _I]),
+    "ds_mesh_sdf_query": (_I, [_P, _I64, _P, _I64, _P, _P, _P, _P, _P, _I64, _P]),
+    # Sinkhorn divergence: sinkhorn.hip
+    "ds_sinkhorn_workspace_floats": (_I64, [_I64, _I64, _I64]),
+    "ds_sinkhorn_bbox": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _P]),
+    "ds_sinkhorn_loop": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _P, _I, _I, _P, _P]),
+    "ds_sinkhorn_final": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P]),
+    "ds_sinkhorn_backward": (_I, [_P, _P, _P, _P, _I64, _I64, _I64, _I64, _F, _I, _P, _P, _P, _P, _P]),
+    # deformation gradient and force gather: deform.hip
+    "ds_deform_tables": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _P, _P, _P]),
+    "ds_deform_gradient": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _I64, _I, _P, _P]),
+    "ds_deform_force": (_I, [_P, _I64, _P, _I64, _I, _P, _P, _P, _P, _P, _I64, _I, _P, _P, _P]),
+    # general tangents: tangent.hip
+    "ds_combine_tangent": (_I, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    "ds_tangent_forms_workspace_bytes": (ctypes.c_size_t, [_I64, _I]),
+    "ds_tangent_forms": (_I, [_P, _P, _P, _I64, _P, _I64, _I, _P, _P, ctypes.c_size_t, _P]),
+    # mode shapes at points: modesample.hip
+    "ds_mode_sample_fwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P]),
+    "ds_mode_sample_bwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P, _P]),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+
+_lib = None
+
+
+def lib():
+    """Load (once) and return the ctypes handle; RuntimeError if the HIP extension is absent."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise RuntimeError(
+                f"diffsound_amd: HIP extension {LIB_PATH} is missing - build it with "
+                "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C diffsound_amd/csrc`. "
+                "There is no CPU fallback.")
+        handle = ctypes.CDLL(LIB_PATH)
+        handle.ds_abi_version.restype = _I
+        got = handle.ds_abi_version()
+        if got != ABI_VERSION:  # a stale build resolves every symbol and would be called with shifted arguments
+            raise RuntimeError(f"diffsound_amd: {LIB_PATH} has ABI version {got}, this package needs {ABI_VERSION} - "
+                               "rebuild it with `make -C diffsound_amd/csrc`")
+        for name, (res, args) in _SIGNATURES.items():
+            fn = getattr(handle, name)
+            fn.restype = res
+            fn.argtypes = args
+        _lib = handle
+    return _lib
+
+
+def check(status, what):
+    if status != 0:
+        msg = lib().ds_last_error()
+        raise RuntimeError(f"{what} failed (status {status}): {msg.decode() if msg else ''}")
+
+
+_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def stream_ptr():
+    """The calling thread's current HIP stream as a pointer-sized int (ctypes converts it for the c_void_p slot).
+    The raw-stream query is the one compiled-kernel launchers use: ~0.3 us against ~9 us for building a
+    torch.cuda.Stream object on every launch (a pass makes ~1000 launches per lane, under the interpreter lock)."""
+    if _raw_stream is not None:
+        return _raw_stream(torch.cuda.current_device())
+    return torch.cuda.current_stream().cuda_stream
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def require_gpu(*tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise RuntimeError("diffsound_amd: tensors must live on the HIP device (no CPU fallback)")
 
 
 _lapack = None
@@ -286,50 +380,6 @@ class blas_one_thread:
                 cls._ctl = None
 
 
-_SIGNATURES["ds_twolevel_apply"] = (_I, [ctypes.POINTER(TwoLevelDesc), _P])
-_SIGNATURES["ds_chebyshev_apply"] = (_I, [ctypes.POINTER(LevelDesc), _P, _I64, _P, _I64, _P, _P, _I64, _I, _P])
-_SIGNATURES["ds_chebyshev_apply16"] = (_I, [ctypes.POINTER(LevelDesc), _P, _I64, _P, _I64, _P, _P, _P, _I64, _I, _P])
-_SIGNATURES["ds_spmm_union16"] = (_I, [_I, _P, _P, _I64, _I, _P, _P, _I64, _I64, _P, _I64, _P, _I64, _I, _P, _I64, _P, _I, _F,
-                                      _F, _I, _P, _I64, _P])
-_SIGNATURES["ds_group_inverse"] = (_I, [_P, _P, _P, _I64, _I, _P, _P])
-_SIGNATURES["ds_group_pack_kc"] = (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _P, _P])
-_SIGNATURES["ds_group_apply16"] = (_I, [_P, _I, _P, _I, _I64, _P, _I, _I64, _I64, _I, _P])
-_SIGNATURES["ds_cheb_init16"] = (_I, [_P, _I, _I64, _P, _I64, _P, _I64, _P, _I64, _I, _F, _P])
-_SIGNATURES["ds_scalar_csr_spmm16"] = (_I, [_P, _P, _P, _I64, _P, _I64, _P, _I64, _I, _F, _P])
-_SIGNATURES["ds_lobpcg_iterate"] = (_I, [ctypes.POINTER(LobpcgDesc), ctypes.POINTER(LapackTable), _P])
-_SIGNATURES["ds_host_wait_mode"] = (_I, [_I])
-_SIGNATURES["ds_selftest_dense"] = (_I, [ctypes.POINTER(LapackTable), _I, _I, ctypes.c_uint, ctypes.POINTER(_D)])
-_SIGNATURES["ds_host_start_block"] = (_I, [ctypes.POINTER(LapackTable), _P, _I, _I, _D, _D, _P, _P, _P, ctypes.POINTER(_D), ctypes.POINTER(_I)])
-_SIGNATURES["ds_host_polish"] = (_I, [ctypes.POINTER(LapackTable), _I, _P, _P, _P, _I, _I, _P, _P, _P])
-_SIGNATURES["ds_host_raw_basis"] = (_I, [ctypes.POINTER(LapackTable), _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P, ctypes.POINTER(_I)])
-_SIGNATURES["ds_host_rr_step"] = (_I, [ctypes.POINTER(LapackTable), _P, _I, _I, _P, _P, _P])
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
-_lib = None
-
-
-def lib():
-    """Load (once) and return the ctypes handle; RuntimeError if the HIP extension is absent."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise RuntimeError(
-                f"diffsound_amd: HIP extension {LIB_PATH} is missing - build it with "
-                "`python -c 'import __graft_entry__ as g; g.build()'` or `make -C diffsound_amd/csrc`. "
-                "There is no CPU fallback.")
-        handle = ctypes.CDLL(LIB_PATH)
-        handle.ds_abi_version.restype = _I
-        got = handle.ds_abi_version()
-        if got != ABI_VERSION:  # a stale build resolves every symbol and would be called with shifted arguments
-            raise RuntimeError(f"diffsound_amd: {LIB_PATH} has ABI version {got}, this package needs {ABI_VERSION} - "
-                               "rebuild it with `make -C diffsound_amd/csrc`")
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(handle, name)
-            fn.restype = res
-            fn.argtypes = args
-        _lib = handle
-    return _lib
-
-
 def host_start_block(G, ny, b, ortho_tol, eps):
     """ds_host_start_block on a host fp64 tensor G ((ny + b) x 2 b): (lam, coef, cx, amp) as host tensors, or None when the caller
     has to take the explicit route."""
@@ -383,34 +433,6 @@ def host_rr_step(G, na):
         check(lib().ds_host_rr_step(ctypes.byref(lapack_table()), G.data_ptr(), sz, na, E.data_ptr(), Z1.data_ptr(), Zp.data_ptr()),
               "ds_host_rr_step")
     return E, Z1, Zp
-
-
-def check(status, what):
-    if status != 0:
-        msg = lib().ds_last_error()
-        raise RuntimeError(f"{what} failed (status {status}): {msg.decode() if msg else ''}")
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def stream_ptr():
-    """The calling thread's current HIP stream as a pointer-sized int (ctypes converts it for the c_void_p slot).
-    The raw-stream query is the one compiled-kernel launchers use: ~0.3 us against ~9 us for building a
-    torch.cuda.Stream object on every launch (a pass makes ~1000 launches per lane, under the interpreter lock)."""
-    if _raw_stream is not None:
-        return _raw_stream(torch.cuda.current_device())
-    return torch.cuda.current_stream().cuda_stream
-
-
-def ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def require_gpu(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError("diffsound_amd: tensors must live on the HIP device (no CPU fallback)")
 
 
 class Pattern:

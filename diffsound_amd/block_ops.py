@@ -1,5 +1,5 @@
 """HIP implementation of the eigensolver's ``ops`` protocol on a BSR-3 pattern: the part ``HipModalOps`` and ``HipSparseOps``
-(modal_ops.py) share.  Every product, Gram, mix, residual and both native drivers are one call into libdiffsound_hip.so here;
+(hip_ops.py) share.  Every product, Gram, mix, residual and both native drivers are one call into libdiffsound_hip.so here;
 what decides node ordering and tables stays in modal_ops.py.
 No operation here has a CPU implementation; tensors must be HIP tensors.
 """

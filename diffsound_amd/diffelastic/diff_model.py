@@ -52,7 +52,8 @@ import torch.nn as nn
 
 from ..ddsp.oscillator import WeightedParam
 from ..lobpcg.modal_solver import ModalSolver, SolverConfig, tuned_config
-from ..modal_ops import HipModalOps, TetSystem, isotropic_tangent
+from ..hip_ops import HipModalOps, isotropic_tangent
+from ..modal_ops import TetSystem
 from .material_model import Material, MatSet
 from .mesh import TetMesh
 

@@ -97,7 +97,7 @@ def _pad_pencil(A, B, pad):
 
 def _solve(A, B, k, X, E, n, iK, niter, tol, largest, method, tracker, ortho_iparams, ortho_fparams,
            ortho_bparams, return_rerr):
-    from ..modal_ops import HipSparseOps
+    from ..hip_ops import HipSparseOps
 
     method = "ortho" if method is None else method
     if method not in ("ortho", "basic"):

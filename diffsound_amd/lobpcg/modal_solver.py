@@ -21,7 +21,7 @@ The module is split by concern: ``config.py`` (SolverConfig, tuned_config, Modal
 host algebra and its one-thread guard), ``precond.py`` (the preconditioners), ``refine.py`` (the fp64 refinement behind
 ``ModalSolver.refine64``, in named phases); every name stays importable from here.
 
-The ``ops`` protocol (``diffsound_amd/modal_ops.py``: the HIP implementation; ``oracle/ops_cpu.py``: the CPU stand-in).
+The ``ops`` protocol (``diffsound_amd/hip_ops.py`` on ``block_ops.py``: the HIP implementation; ``oracle/ops_cpu.py``: the CPU stand-in).
 
 Required:
   n, device, dtype, rigid (n x 6 M-orthonormal, or None), counts,

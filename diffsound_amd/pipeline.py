@@ -21,7 +21,8 @@ from .ddsp.oscillator import TraditionalDampedOscillator
 from .diffelastic.material_model import Material
 from .lobpcg.modal_solver import ModalSolver, SolverConfig
 from . import _hip
-from .modal_ops import HipModalOps, TetSystem
+from .hip_ops import HipModalOps
+from .modal_ops import TetSystem
 
 
 class DirectLinear(nn.Module):

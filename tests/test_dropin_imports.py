@@ -4,6 +4,8 @@ The name list is a committed fixture generated from the reference with ``ast`` (
 import importlib
 import json
 import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -11,6 +13,12 @@ import torch
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FIX = json.load(open(os.path.join(HERE, "golden", "experiment_imports.json")))
+# what was importable from diffsound_amd.modal_ops before the operators moved to hip_ops.py, by the module that holds it now
+MODAL_OPS_SURFACE = {
+    "modal_ops": ["TetSystem", "morton_order", "UNION_CAP", "MF_BATCH", "MF_TAIL", "MF32_BATCH", "MF32_G"],
+    "hip_ops": ["HipModalOps", "HipSparseOps", "isotropic_tangent", "_coo_to_bsr3"],
+    "block_ops": ["DS_F32", "DS_F64", "_HipBlockOps", "_ld"],
+}
 
 
 @pytest.mark.parametrize("module", sorted(FIX["in_scope"]))
@@ -103,3 +111,28 @@ def test_plot_spec_returns_a_figure():
     assert img.shape == (33, 40)
     import matplotlib.pyplot as plt
     plt.close(fig)
+
+
+@pytest.mark.parametrize("first", ["hip_ops", "modal_ops"])
+def test_modal_ops_keeps_its_names_whichever_module_loads_first(first):
+    """In a fresh interpreter that imports ``first`` before the other: every name of the earlier surface of modal_ops resolves
+    from modal_ops, as an attribute and by ``from ... import``, to the object in its new home - without loading the library."""
+    code = f"""
+import importlib, json, sys
+importlib.import_module("diffsound_amd.{first}")
+from diffsound_amd import modal_ops, _hip
+for home, names in json.loads(sys.argv[1]).items():
+    mod = importlib.import_module("diffsound_amd." + home)
+    for name in names:
+        scope = {{}}
+        exec("from diffsound_amd.modal_ops import " + name, scope)
+        assert getattr(modal_ops, name) is vars(mod)[name] and scope[name] is vars(mod)[name], (home, name)
+assert _hip._lib is None
+try:
+    modal_ops.no_such_name
+except AttributeError:
+    print("resolved")
+"""
+    run = subprocess.run([sys.executable, "-c", code, json.dumps(MODAL_OPS_SURFACE)], cwd=os.path.dirname(HERE),
+                         capture_output=True, text=True)
+    assert run.returncode == 0 and run.stdout.strip() == "resolved", run.stderr

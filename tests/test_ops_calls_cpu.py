@@ -1,4 +1,4 @@
-"""The launches of the HIP operator layer (diffsound_amd/modal_ops.py, block_ops.py), pinned without a GPU.
+"""The launches of the HIP operator layer (diffsound_amd/modal_ops.py, hip_ops.py, block_ops.py), pinned without a GPU.
 
 The library loads on the host and its symbolic routines run there; every operator method is then run on CPU tensors against a
 stub library that records each call - the symbol and every argument, pointers as (name of the tensor they fall into, byte offset
@@ -15,12 +15,11 @@ from types import SimpleNamespace
 import pytest
 import torch
 
-from diffsound_amd import _hip, fem_tables, meshgen, modal_ops
+from diffsound_amd import _hip, meshgen, modal_ops
 from diffsound_amd.lobpcg import precond as pc
 from oracle import fem
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ops_call_traces.json")
-CPU = torch.device("cpu")
 _TetSystem, _HipModalOps = modal_ops.TetSystem, modal_ops.HipModalOps
 # (pointer argument -> its count argument) of the calls that take an array of ds_block64_t by address
 _BLOCK_TABLES = {"ds_mix64": {1: 0}, "ds_gram64_blocks": {1: 0, 3: 2}}
@@ -122,38 +121,40 @@ class Recorder:
         return 4096 if "_workspace_" in symbol else 0
 
 
+def _host_pattern(tets, nv, cap):
+    """What _hip.DevicePattern hands the constructor, from the library's host routines on CPU tensors."""
+    pat = _hip.Pattern(tets, nv)
+    g = _hip.Groups(pat.rowptr, pat.colidx, nv)
+    pat.ne, pat.gent, pat.kperm, pat.ngroups = g.ne, g.gent, g.kperm, g.ngroups
+    pat.utab, pat.ctab = _hip.union_chunks(g.gptr, g.goff, cap)
+    pat.single = pat.ctab.shape[0] == pat.utab.shape[0]
+    return pat
+
+
 def _stand_in(vertices, tets, order, density, reorder=True):
-    """What TetSystem.__init__ builds, from the library's host routines and CPU tensors (no assembly: the values stay zero)."""
+    """What TetSystem.__init__ builds, by the constructor's own steps on CPU tensors: only the pattern comes from elsewhere, and
+    there is no assembly (the values stay zero)."""
     s = object.__new__(_TetSystem)
-    s.order, s.N, s.device = int(order), fem_tables.NODES_PER_TET[int(order)], CPU
-    if reorder:
-        s.perm = modal_ops.morton_order(vertices)
-        s.inv_perm = torch.empty_like(s.perm)
-        s.inv_perm[s.perm] = torch.arange(vertices.shape[0])
-        s.vertices = vertices.detach().to(torch.float32)[s.perm].contiguous()
-        s.tets = s.inv_perm[tets.long()].to(torch.int32).contiguous()
-    else:
-        s.perm = s.inv_perm = None
-        s.vertices = vertices.detach().to(torch.float32).contiguous().clone()
-        s.tets = tets.to(torch.int32).contiguous()
-    s.nv, s.T, s.density = s.vertices.shape[0], s.tets.shape[0], float(density)
-    s.n = 3 * s.nv
-    pat = _hip.Pattern(s.tets, s.nv)
-    s.nnzb = pat.nnzb
-    s.rowptr, s.colidx, s.diagidx, s.cptr, s.clist = pat.rowptr, pat.colidx, pat.diagidx, pat.cptr, pat.clist
-    s.dtab = torch.from_numpy(fem_tables.stiffness_table(s.order))
-    s.mtab = torch.from_numpy(fem_tables.mass_table(s.order, s.density))
-    s.klam = torch.zeros((s.nnzb, 9), dtype=torch.float64)
-    s.kmu = torch.zeros((s.nnzb, 9), dtype=torch.float64)
-    s.ms = torch.zeros((s.nnzb,), dtype=torch.float64)
-    s._tetgeo = torch.zeros((s.T, 13), dtype=torch.float64)
-    g = _hip.Groups(pat.rowptr, pat.colidx, s.nv)
-    ut, ct = _hip.union_chunks(g.gptr, g.goff, modal_ops.UNION_CAP)
-    s.groups = dict(ne=g.ne, gent=g.gent, kperm=g.kperm, kperm64=g.kperm.long(),
-                    union=dict(utab=ut, ctab=ct, capb=modal_ops.UNION_CAP, ngroups=g.ngroups, single=ct.shape[0] == ut.shape[0]))
-    s._coarse = s._cinc = s._grad_rule = None
-    s._mfma_tables = {}
+    s._number_nodes(vertices, tets, order, density, reorder)
+    s._take_pattern(_host_pattern(s.tets, s.nv, modal_ops.UNION_CAP))
+    s._element_tables_and_values()
+    s._lazy_slots()
+    for values in (s.klam, s.kmu, s.ms, s._tetgeo):
+        values.zero_()
     return s
+
+
+def test_stand_in_has_the_attributes_the_constructor_sets(monkeypatch):
+    """The constructor itself, run on the host with its pattern source replaced and its assembly skipped, sets exactly the
+    instance attributes of the stand-in: an attribute added to TetSystem.__init__ outside the shared steps fails here."""
+    v, t = meshgen.kuhn_box(2)
+    v, t = torch.from_numpy(v).float(), torch.from_numpy(t).long()
+    monkeypatch.setattr(_hip, "require_gpu", lambda *tensors: None)
+    monkeypatch.setattr(_hip, "DevicePattern", _host_pattern)
+    monkeypatch.setattr(_TetSystem, "assemble", lambda self, vertices=None: None)
+    for reorder in (True, False):
+        built = vars(_TetSystem(v, t, 1, 2700.0, reorder))
+        assert built and sorted(built) == sorted(vars(_stand_in(v, t, 1, 2700.0, reorder)))
 
 
 class Env:

@@ -92,7 +92,7 @@ Collected by `tools/collect_profiles.sh r05 <part>` on the GPU box (this file: `
 | `r05_order_ab.txt`, `r05_nested_knobs.txt`, `r05_lanes_sync_sweep.txt`, `r05_concurrency_profile.txt`, `r05_device_slots_experiment.txt`, `r05_host_profile_one_lane.txt` | experiments of the round that changed nothing in the product: bricks along a Hilbert curve (same kernel times, 2.5 % more traffic); the nested start's own polynomial (flat optimum); 12 / 16 hypotheses in flight and the host's wait modes (slower than 8); how many kernels overlap in the 8-lane run and where the device idles; a gate that lets only 8 solves on the device of 16 hypotheses in flight (+3 % for twice the HBM); cProfile of one hypothesis at a time (`ds_lobpcg_iterate` 83 % of a pass's host time) |
 | `r05_mf_tail.txt` | the bf16 term kernel's round trips: a wave's head in ONE (fixed-stride records of a group's first 64 entries: 110.9–112.6 → 108.0–109.2 µs), what the fifth batch of a 65-entry group costs (a timing-only build without it: 106.3 → 94.3 µs), the tail form (the last batch takes two entries more, bit-identical): **97.7–98.0 µs = 0.489 of 8 TB/s** |
 | `r05_nt_hint_ab.txt`, `r05_nt_epi_ab.txt` | four library builds on one box: non-temporal hints on the value / table loads (nt1), on the result stores (nt2), both (nt3) — K W 182 → 177 / 169 µs, M W 149 → 130 / 129, bf16 term 117 → 112 (loads) / 111 (both), corner-node level +4 % with the load hint (kept off there); the same hint on the epilogue's once-read operands costs 6 % (not adopted) |
-| `spmm_pmc_bytes_per_launch.json`, `r05_spmm_pmc_{{fp32,bf16,mfma,kx,km,resid}}.json` | HBM-side traffic per launch from separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes; bytes = (2·FETCH + WRITE)·1024 (gfx950 correction of `guides/MI355X_MICROARCH.md`); keyed by the hash of the SpMM sources + `modal_ops.py` — `bench.py` reports a record with another hash as stale |
+| `spmm_pmc_bytes_per_launch.json`, `r05_spmm_pmc_{{fp32,bf16,mfma,kx,km,resid}}.json` | HBM-side traffic per launch from separate `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` passes; bytes = (2·FETCH + WRITE)·1024 (gfx950 correction of `guides/MI355X_MICROARCH.md`); keyed by the hash of the SpMM sources + `modal_ops.py` (the node ordering and the union / MFMA tables; the operators of `hip_ops.py` are not part of the key) — `bench.py` reports a record with another hash as stale |
 | `gram_mix_mfma_util.json`, `r05_gram_mix.txt` | matrix-pipe utilisation of the Rayleigh-Ritz kernels per shape (one shape per profiled process: `SQ_VALU_MFMA_BUSY_CYCLES` ÷ (`GRBM_GUI_ACTIVE`/8 × 1 024 SIMDs)), keyed by the hash of `gram.hip` + `blockops.hip`; timings at the solver's shapes |
 | `r05_mb_solver_spmm.txt`, `r05_mb_narrow.txt`, `r05_mb_corner.txt`, `r05_mb_kx.txt` | the SpMM forms of one iteration alone on the solver's operand layout; the narrow-block kernel against the production kernel (8 / 16 columns: K X 131 → 115 µs on the fine level, slower for M X and on the corner-node level: used for the fine level's K X only); the corner-node level; K X / M X on compact blocks |
 | `r05_host_time_one_lane.txt`, `r05_host_eigh_probe.txt` | where the host time of ONE hypothesis at a time goes (`DS_EXP_TIMING=1`: per solve, waiting for the stream / `dsyevd` / `dgemm` / rest; per pass, by stage with a synchronisation per stage; the first pass of the file is the set-up pass) and host LAPACK timings of the Ritz problem on the EPYC host (dsyevd 240: 2.35 ms standalone, ssyevd 1.52, dsyevr lowest third 4.6, torch/MKL 2.9; dgemm 119 GF/s on one thread) |
