@@ -216,7 +216,15 @@ _SIGNATURES = {
     "ds_mode_sample_fwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P]),
     "ds_mode_sample_bwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P, _P]),
 }
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
+# Sliding contact: osc_slide.hip.  A literal of its own: tests/test_osc_refusals_cpu.py holds one refusal table for every
+# ds_osc_* entry of _SIGNATURES and is complete as it stands; the refusals of these three are tabled in
+# tests/test_osc_slide_cabi_cpu.py.  Bound, exported and checked against the header like every other entry.
+_SIGNATURES_SLIDE = {
+    "ds_osc_slide_workspace_bytes": (_I64, [_I, _I, _I, _I, _I]),
+    "ds_osc_slide_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
+    "ds_osc_slide_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P]),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SLIDE)
 
 _lib = None
 
@@ -236,7 +244,7 @@ def lib():
         if got != ABI_VERSION:  # a stale build resolves every symbol and would be called with shifted arguments
             raise RuntimeError(f"diffsound_amd: {LIB_PATH} has ABI version {got}, this package needs {ABI_VERSION} - "
                                "rebuild it with `make -C diffsound_amd/csrc`")
-        for name, (res, args) in _SIGNATURES.items():
+        for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_SLIDE.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

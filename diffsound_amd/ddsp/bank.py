@@ -1,14 +1,17 @@
-"""The oscillator banks as functions of tensors: three ``torch.autograd.Function`` wrappers, one per kernel family, and their
+"""The oscillator banks as functions of tensors: four ``torch.autograd.Function`` wrappers, one per kernel family, and their
 functional entries.  ``_OscBank`` is the closed-form bank with the force as a causal FIR out of LDS (ds_osc_bank_fwd / _bwd,
 csrc/oscillator.hip), ``_OscBankTV`` the bank with per-sample rates (ds_osc_tv_fwd / _bwd, same file), ``_OscDriven`` the
-recursive resonator under a force of any length, with a force gradient (ds_osc_driven_fwd / _bwd, csrc/osc_driven.hip).
-What the three share - operand preparation, the optional ``amp`` across save_for_backward, the gradient buffers - is written
+recursive resonator under a force of any length, with a force gradient (ds_osc_driven_fwd / _bwd, csrc/osc_driven.hip),
+``_OscSliding`` the same resonator with an input gain per mode and per sample, a contact that moves while the force acts
+(ds_osc_slide_fwd / _bwd, csrc/osc_slide.hip).
+What they share - operand preparation, the optional ``amp`` across save_for_backward, the gradient buffers - is written
 once below; a ``forward`` / ``backward`` holds its entry point, its workspace and its extra gradient."""
 import torch
 
 from .. import _hip
 
 FIR_MAX_FORCE = 512  # taps the FIR kernels of csrc/oscillator.hip hold in LDS (MAXF)
+SLIDE_HOP_UNIT = 16  # samples per lane of csrc/osc_slide.hip (DS_OSC_SCAN_RUN): the sliding bank's hop is a multiple of it
 
 
 def _prepare(dtype, d, w, amp, force):
@@ -129,6 +132,65 @@ class _OscDriven(torch.autograd.Function):
         _hip.check(L.ds_osc_driven_bwd(p(gy), p(d), p(w), p(amp), p(force), A, m, nF, ctx.S, ctx.sr, p(work), nbytes, p(gd),
                                        p(gw), p(gamp), p(gforce), _hip.stream_ptr()), "ds_osc_driven_bwd")
         return gd, gw, gamp, gforce, None, None
+
+
+class _OscSliding(torch.autograd.Function):
+    """The driven bank with an input gain per mode and per sample, x[t] = z (x[t-1] + g[t] force[t]), g piecewise linear
+    between the K frames of ``gain`` (A, K, m), ``hop`` samples apart, the last one held (ds_osc_slide_fwd / ds_osc_slide_bwd,
+    csrc/osc_slide.hip): a contact that moves while the force acts.  Gradients for d, w, amp, force and gain."""
+
+    @staticmethod
+    def _work(L, A, m, S, K, hop, device):
+        nbytes = L.ds_osc_slide_workspace_bytes(A, m, S, K, hop)
+        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+    @staticmethod
+    def forward(ctx, d, w, amp, force, gain, hop, S, sr):
+        d, w, amp, force = _prepare(torch.float64, d, w, amp, force)
+        _hip.require_gpu(gain)
+        A, nF = force.shape
+        m = d.shape[0]
+        if gain.dim() != 3 or gain.shape[0] != A or gain.shape[2] != m or gain.shape[1] < 1:
+            raise ValueError(f"sliding bank: gain must be ({A}, K, {m}), got {tuple(gain.shape)}")
+        if hop <= 0 or hop % SLIDE_HOP_UNIT:
+            raise ValueError(f"sliding bank: hop = {hop} is not a positive multiple of {SLIDE_HOP_UNIT}")
+        K = gain.shape[1]
+        gain_k = gain.detach().float().transpose(1, 2).contiguous()  # the kernels' layout: (A, m, K), frames contiguous
+        L = _hip.lib()
+        work, nbytes = _OscSliding._work(L, A, m, S, K, hop, force.device)
+        y = torch.empty((A, S), dtype=torch.float32, device=force.device)
+        p = _hip.ptr
+        _hip.check(L.ds_osc_slide_fwd(p(d), p(w), p(amp), p(force), p(gain_k), A, m, nF, S, K, hop, float(sr), p(work), nbytes,
+                                      p(y), _hip.stream_ptr()), "ds_osc_slide_fwd")
+        _save(ctx, d, w, amp, force, S, sr)
+        ctx.gain_k, ctx.hop, ctx.gain_dtype = gain_k, hop, gain.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        d, w, amp, force, gy = _restore(ctx, gy)
+        gain_k, hop = ctx.gain_k, ctx.hop
+        A, nF = force.shape
+        m, K = d.shape[0], gain_k.shape[2]
+        L = _hip.lib()
+        work, nbytes = _OscSliding._work(L, A, m, ctx.S, K, hop, gy.device)
+        gd, gw, gamp = _grad_buffers(d, w, amp)
+        gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
+        ggain = torch.empty_like(gain_k) if ctx.needs_input_grad[4] else None
+        p = _hip.ptr
+        _hip.check(L.ds_osc_slide_bwd(p(gy), p(d), p(w), p(amp), p(force), p(gain_k), A, m, nF, ctx.S, K, hop, ctx.sr, p(work),
+                                      nbytes, p(gd), p(gw), p(gamp), p(gforce), p(ggain), _hip.stream_ptr()),
+                   "ds_osc_slide_bwd")
+        if ggain is not None:
+            ggain = ggain.transpose(1, 2).to(ctx.gain_dtype)
+        return gd, gw, gamp, gforce, ggain, None, None, None
+
+
+def oscillator_bank_sliding(d, w, amp, force, gain, hop, sample_num, sr):
+    """The bank under a contact that slides: ``oscillator_bank``'s operands plus ``gain`` (A, K, m), the input gain of every
+    mode at K control frames ``hop`` samples apart (``ContactSurface.path_gains``), linear in between, the last frame held;
+    ``hop`` a positive multiple of 16.  ``amp`` stays the output amplitude.  Autograd reaches d, w, amp, force and gain."""
+    return _OscSliding.apply(d, w, amp, force, gain, int(hop), int(sample_num), float(sr))
 
 
 def oscillator_bank_tv(dmp, frq, amp, force, sample_num, sr):

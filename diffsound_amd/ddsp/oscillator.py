@@ -4,7 +4,9 @@ Class names, constructor arguments, ``forward`` signatures, returned shapes/dtyp
 ``damped_freq`` attribute follow the reference; the (A, m, S) signal path itself is ONE fused HIP
 kernel (``ds_osc_bank_fwd`` / ``ds_osc_bank_bwd``) wrapped in a ``torch.autograd.Function``; a force of more
 than 512 taps, or one that is itself trained (``train_forces=True``), renders through the recursive-resonator
-kernels (``ds_osc_driven_fwd`` / ``ds_osc_driven_bwd``), which also return the force gradient.
+kernels (``ds_osc_driven_fwd`` / ``ds_osc_driven_bwd``), which also return the force gradient; a 3-D ``mode_gain``
+(audio_num, K, mode_num) with ``gain_hop`` - a contact that slides while the force acts - renders through the sliding bank
+(``ds_osc_slide_fwd`` / ``ds_osc_slide_bwd``).
 The tiny per-mode parameter algebra (softplus-weighted bins, d = (alpha + beta w0^2)/2,
 w = sqrt(w0^2 - d^2)) stays in torch so autograd reaches every learnable leaf exactly as in the
 reference.
@@ -20,8 +22,8 @@ import torch.nn.functional as F
 
 from .. import _hip  # noqa: F401
 from ..diffelastic.material_model import Material, MatSet  # noqa: F401  (re-exported like the reference)
-from .bank import (FIR_MAX_FORCE, _OscBank, _OscBankTV, _OscDriven, oscillator_bank, oscillator_bank_driven,  # noqa: F401
-                   oscillator_bank_tv)
+from .bank import (FIR_MAX_FORCE, SLIDE_HOP_UNIT, _OscBank, _OscBankTV, _OscDriven, _OscSliding,  # noqa: F401
+                   oscillator_bank, oscillator_bank_driven, oscillator_bank_sliding, oscillator_bank_tv)
 from .filtered_noise import (FN_MAX_COEFF, FN_MAX_FRAME, FilteredNoise, _FilteredNoiseFn,  # noqa: F401
                              _filtered_noise_torch)
 from .utils import modifed_sigmoid
@@ -116,8 +118,9 @@ class _BankBase(nn.Module):
             self._force = self._force.to(dev)
         return dev, self._force
 
-    def _render(self, freq_linear, alpha, beta, amp):
-        """freq_linear (m,1) or (m,) any float dtype; alpha/beta python floats or (1,m,1) tensors; amp (A,m,1)|None."""
+    def _render(self, freq_linear, alpha, beta, amp, slide=None):
+        """freq_linear (m,1) or (m,) any float dtype; alpha/beta python floats or (1,m,1) tensors; amp (A,m,1)|None;
+        slide: None, or the (gain (A, K, m), hop) of ``_sliding`` - the render then goes through the sliding bank."""
         dev, force = self._force_on_device()
         f = freq_linear.reshape(self.mode_num).to(dev).double()
         w0sq = (f * (2 * np.pi)) ** 2
@@ -130,7 +133,30 @@ class _BankBase(nn.Module):
         fd = (w / (2 * np.pi)).float()
         self.damped_freq = fd.reshape(1, self.mode_num, 1).expand(self.audio_num, self.mode_num, self.sample_num)
         a = None if amp is None else amp.reshape(self.audio_num, self.mode_num).to(dev)
+        if slide is not None:
+            return oscillator_bank_sliding(d, w, a, force, slide[0].to(dev), slide[1], self.sample_num, self.sr)
         return oscillator_bank(d, w, a, force, self.sample_num, self.sr)
+
+    def _sliding(self, mode_gain, gain_hop, time_varying=False):
+        """None for ``mode_gain`` = None or a 2-D gain (``_with_gain`` takes those).  For a 3-D gain (audio_num, K, mode_num)
+        - the input gains of a contact that moves, one frame every ``gain_hop`` samples
+        (``diffsound_amd.impact.ContactSurface.path_gains``) - the pair (mode_gain, gain_hop) for the sliding bank, after
+        the checks that need no device: ValueError for a missing ``gain_hop``, one that is not a positive multiple of 16,
+        a gain of another shape, or the time-varying render, which has no sliding form."""
+        if not torch.is_tensor(mode_gain) or mode_gain.dim() != 3:
+            if gain_hop is not None:
+                raise ValueError("gain_hop goes with a 3-D mode_gain (audio_num, K, mode_num)")
+            return None
+        if gain_hop is None:
+            raise ValueError("a 3-D mode_gain (audio_num, K, mode_num) needs gain_hop, the samples between two frames")
+        if int(gain_hop) != gain_hop or gain_hop <= 0 or int(gain_hop) % SLIDE_HOP_UNIT:
+            raise ValueError(f"gain_hop = {gain_hop} is not a positive multiple of {SLIDE_HOP_UNIT}")
+        if mode_gain.shape[0] != self.audio_num or mode_gain.shape[2] != self.mode_num or mode_gain.shape[1] < 1:
+            raise ValueError(f"a 3-D mode_gain must be ({self.audio_num}, K, {self.mode_num}), got {tuple(mode_gain.shape)}")
+        if time_varying:
+            raise ValueError("a 3-D mode_gain (a sliding contact) renders through the closed-form bank only: "
+                             "non_linear_rate must be 0")
+        return mode_gain, int(gain_hop)
 
     def _with_gain(self, amp, mode_gain):
         """``amp`` (A, m, 1) or None (unit amplitudes) times ``mode_gain`` (audio_num, mode_num): the gains of a strike
@@ -156,8 +182,10 @@ class TraditionalDampedOscillator(_BankBase):
         self.alpha = mat.alpha
         self.beta = mat.beta
 
-    def forward(self, freq_linear, mode_gain=None):
-        sig = self._render(freq_linear, float(self.alpha), float(self.beta), self._with_gain(None, mode_gain))
+    def forward(self, freq_linear, mode_gain=None, gain_hop=None):
+        slide = self._sliding(mode_gain, gain_hop)
+        sig = self._render(freq_linear, float(self.alpha), float(self.beta),
+                           None if slide else self._with_gain(None, mode_gain), slide)
         w = self.damped_freq[0, :, 0].double() * (2 * np.pi)
         self.undamped_freq = freq_linear.reshape(1, self.mode_num, 1).to(w.device)
         return sig
@@ -179,8 +207,10 @@ class DampedOscillator(_BankBase):
         # unused by forward(), kept so that the reference's checkpoints load strictly (oscillator.py:78: "just for load")
         self.noise = FilteredNoise(audio_num, 8000)
 
-    def forward(self, freq_linear, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None):
-        return self._render(freq_linear, self.alpha(), self.beta(), self._with_gain(self.amp(), mode_gain))
+    def forward(self, freq_linear, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None, gain_hop=None):
+        slide = self._sliding(mode_gain, gain_hop)
+        amp = self.amp() if slide else self._with_gain(self.amp(), mode_gain)
+        return self._render(freq_linear, self.alpha(), self.beta(), amp, slide)
 
     def _curve_render(self, freq_linear, damping_curve):
         dev, force = self._force_on_device()
@@ -268,11 +298,13 @@ class GTDampedOscillator(_BankBase):
         lbd = (self.freq_linear() * 2 * np.pi) ** 2
         return 0.5 * (self.alpha() + self.beta() * lbd)
 
-    def forward(self, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None):
+    def forward(self, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None, gain_hop=None):
+        slide = self._sliding(mode_gain, gain_hop, time_varying=non_linear_rate != 0.0)
         if non_linear_rate != 0.0:
             sig = self._render_time_varying(non_linear_rate, mode_gain)
         else:
-            sig = self._render(self.freq_linear(), self.alpha(), self.beta(), self._with_gain(self.amp(), mode_gain))
+            amp = self.amp() if slide else self._with_gain(self.amp(), mode_gain)
+            sig = self._render(self.freq_linear(), self.alpha(), self.beta(), amp, slide)
             fd = self.damped_freq[0, :, 0].double()
             d = self.damping().reshape(-1).double().to(fd.device)
             self.undamped_freq = (torch.sqrt((2 * np.pi * fd) ** 2 + d ** 2) / (2 * np.pi)).float().reshape(1, -1, 1)

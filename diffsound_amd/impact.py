@@ -233,6 +233,20 @@ class ContactSurface:
         """``amplitudes(*locate(points), direction)``: differentiable in ``points``."""
         return self.amplitudes(*self.locate(points), direction)
 
+    def path_gains(self, points, direction="normal"):
+        """Gains (A, K, m) fp64 along a contact path: ``points`` (K, 3) - one clip - or (A, K, 3), the contact point at K
+        control frames.  ``amplitudes_at`` on all A K points at once, so differentiable in ``points``; the result is the
+        3-D ``mode_gain`` of the oscillator modules and the ``gain`` of ``ddsp.bank.oscillator_bank_sliding``, which
+        interpolate it linearly between the frames.  ``direction``: "normal", or a tensor shaped like ``points`` or (3,)."""
+        if not isinstance(points, torch.Tensor) or points.dim() not in (2, 3) or points.shape[-1] != 3 or points.numel() == 0:
+            raise ValueError("ContactSurface.path_gains: points must be a (K, 3) or (A, K, 3) tensor, got "
+                             f"{tuple(points.shape) if isinstance(points, torch.Tensor) else type(points).__name__}")
+        lead = (1, points.shape[0]) if points.dim() == 2 else tuple(points.shape[:2])
+        if isinstance(direction, torch.Tensor) and direction.shape == points.shape:
+            direction = direction.reshape(-1, 3)
+        gains = self.amplitudes_at(points.reshape(-1, 3), direction)
+        return gains.reshape(*lead, gains.shape[1])
+
     def amplitude_map(self, direction="normal"):
         """Gains (num_faces, m) fp64 at every face centroid, in one launch: the map to compare measured gains with."""
         face = torch.arange(self.num_faces, device=self.device)

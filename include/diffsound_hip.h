@@ -691,6 +691,35 @@ int ds_osc_driven_bwd(const float* gy, const double* d, const double* w, const f
                       int F, int S, double sr, void* work, int64_t work_bytes, double* gd, double* gw, float* gamp /*or NULL*/,
                       float* gforce /*or NULL, A x F*/, ds_stream_t stream);
 
+/* Sliding contact (still ABI 45, three added symbols): the driven bank above with an input gain per mode AND per sample - a
+ * scrape, a roll or a bow stroke, whose contact point moves while the force acts, so that the gain c_i(p(t)) of mode i
+ * multiplies the force BEFORE the resonator.  The reference has no counterpart (its amp, src/ddsp/oscillator.py:76, is one
+ * free number per clip and mode).
+ *   x_m[t] = z_m (x_m[t-1] + g_m[a,t] force[a,t]),  x[-1] = 0,  force[t] = 0 for t >= F ;  y[a,t] = sum_m amp[a,m] Im x_m[t]
+ *   g_m[a,t] = (1 - th) gain[a,m,k] + th gain[a,m,min(k+1, K-1)],  k = min(t / hop, K-1),  th = (t - k hop) / hop, and th = 0
+ *   where t / hop >= K-1: piecewise linear between K control frames hop samples apart, the last frame held; th and the
+ *   interpolation in fp64 from the fp32 gains.  K = 1 is a constant input gain; unit gains give ds_osc_driven_fwd's y.
+ * Backward with l[t] = z (l[t+1] + gy[t]), l[S] = 0 and gin_m[j] = amp_m Im l_m[j]:
+ *   gforce[a,j] = sum_m g_m[a,j] gin_m[j] for j < min(F, S), exactly 0 for S <= j < F ;
+ *   ggain[a,m,k] = sum_j hat_k(j) force[a,j] gin_m[j], hat_k the two interpolation weights (the clamped ones land on K-1),
+ *   exactly 0 for a frame that no driven sample touches ;  gamp[a,m] = sum_t gy Im x ;
+ *   G_m = sum_a amp sum_t (x[t-1] + g force[t]) l[t] (complex product),  gd = -Im G / sr,  gw = Re G / sr.
+ * gain, ggain: (A x m x K) f32, the frames contiguous.  hop: a positive multiple of DS_OSC_SCAN_RUN (a lane's run of samples
+ * then lies inside one frame interval).  Everything else as ds_osc_driven_fwd / _bwd: dtypes, NULL amp / gamp / gforce (and
+ * ggain), A <= 65535, work of ds_osc_slide_workspace_bytes(A, m, S, K, hop) bytes (0 for arguments that would be refused),
+ * 16-byte aligned, fp64 states, closed-form powers, one fp32 rounding per stored element, no atomics, the same bits from the
+ * same inputs, asynchronous, no allocation.  Refused (DS_ERR_ARG, message in ds_last_error()): a null required pointer;
+ * A, m, F, S or K <= 0; A > 65535; hop <= 0 or no multiple of DS_OSC_SCAN_RUN; sr <= 0; work_bytes below the query; a
+ * misaligned workspace or operand. */
+#define DS_OSC_SCAN_RUN 16 /* samples per wavefront lane of the recursive-resonator kernels: the unit of hop */
+int64_t ds_osc_slide_workspace_bytes(int A, int m, int S, int K, int hop);
+int ds_osc_slide_fwd(const double* d, const double* w, const float* amp, const float* force, const float* gain, int A, int m,
+                     int F, int S, int K, int hop, double sr, void* work, int64_t work_bytes, float* y, ds_stream_t stream);
+int ds_osc_slide_bwd(const float* gy, const double* d, const double* w, const float* amp, const float* force, const float* gain,
+                     int A, int m, int F, int S, int K, int hop, double sr, void* work, int64_t work_bytes, double* gd, double* gw,
+                     float* gamp /*or NULL*/, float* gforce /*or NULL, A x F*/, float* ggain /*or NULL, A x m x K*/,
+                     ds_stream_t stream);
+
 /* Filtered-noise branch (ABI 44; reference src/ddsp/filtered_noise.py:20-67, FilteredNoise.forward and its autograd): per
  * frame of F samples, L logits -> magnitudes -> a Hann-windowed linear-phase FIR of T = 2 L - 1 taps, applied to a white-noise
  * frame and overlap-added at stride F.  nf = S / F + 1 frames.
