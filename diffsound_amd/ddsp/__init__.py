@@ -1,0 +1,1 @@
+from .contact import HertzHammer, contact_force  # noqa: F401

@@ -720,6 +720,36 @@ int ds_osc_slide_bwd(const float* gy, const double* d, const double* w, const fl
                      float* gamp /*or NULL*/, float* gforce /*or NULL, A x F*/, float* ggain /*or NULL, A x m x K*/,
                      ds_stream_t stream);
 
+/* Contact force (still ABI 45, three added symbols): a Hertz hammer - mass[a] > 0, approach speed vel[a], contact stiffness
+ * stiff[a] > 0, exponent p >= 1 (1.5 for Hertz) - coupled to the m modes (d [1/s], w [rad/s, damped]: the banks' pair) of the
+ * object it strikes through the modal gains gain[a,i] at the contact point (ds_mode_sample_fwd).  The reference has no
+ * counterpart.  With h = 1 / (sr R), z_i = exp((-d_i + i w_i) h), kap_i = gain[a,i]^2 / w_i, and xh = 0, vh = vel[a], s_i = 0 at
+ * n = 0, for n = 0 .. F R - 1:
+ *   u = sum_i kap_i Im s_i ;  delta = xh - u ;  f = stiff delta^p where delta > 0, else 0 ;  force[a, n / R] += f / R ;
+ *   vh -= h f / mass ;  xh += h vh ;  s_i = z_i (s_i + h f).
+ * fp64 throughout, force (A x F) stored as f32 (one rounding), as the banks take it.  vel[a] <= 0: the clip's force and all its
+ * gradients are exact zeros.  Explicit: stable while h sqrt(p stiff delta_max^(p-1) (1 / mass + sum_i kap_i w_i)) << 2; a
+ * non-finite result is not detected.  Rigid-body motion of the object is not in the model.
+ * ds_contact_bwd is the exact adjoint of that recursion: from gforce (A x F) f32, gd, gw (m) summed over the clips in ascending
+ * order, ggain (A x m), gmass, gvel, gstiff (A), all f64; gd and gw are both given or both NULL, so are gmass / gvel / gstiff,
+ * ggain may be NULL: what is NULL is not computed into memory.  It runs the forward again and keeps (delta, delta^p) and s_i[n]
+ * of every substep in work: ds_contact_workspace_bytes(A, m, F, R) = 16 (A F R (1 + m) + A m) bytes (0 for arguments that would
+ * be refused), 16-byte aligned.  One wavefront per clip, no atomics, the same bits from the same inputs; asynchronous on the
+ * stream, no allocation, no synchronisation.  Refused (DS_ERR_ARG, message in ds_last_error()): a null required pointer; A
+ * outside 1..65535; m outside 1..DS_CONTACT_MAX_MODES; R outside 1..DS_CONTACT_MAX_OVERSAMPLE; F < 1; F R above
+ * DS_CONTACT_MAX_SUBSTEPS; p < 1 or not finite; sr <= 0; half a gradient pair; work_bytes below the query; a misaligned
+ * workspace or operand. */
+#define DS_CONTACT_MAX_MODES 512       /* 8 modes per wavefront lane, in registers */
+#define DS_CONTACT_MAX_OVERSAMPLE 64   /* R */
+#define DS_CONTACT_MAX_SUBSTEPS 1048576 /* F R */
+int64_t ds_contact_workspace_bytes(int A, int m, int F, int R);
+int ds_contact_fwd(const double* d, const double* w, const double* gain, const double* mass, const double* vel,
+                   const double* stiff, int A, int m, int F, int R, double p, double sr, float* force, ds_stream_t stream);
+int ds_contact_bwd(const float* gforce, const double* d, const double* w, const double* gain, const double* mass,
+                   const double* vel, const double* stiff, int A, int m, int F, int R, double p, double sr, void* work,
+                   int64_t work_bytes, double* gd /*or NULL*/, double* gw /*or NULL*/, double* ggain /*or NULL*/,
+                   double* gmass /*or NULL*/, double* gvel /*or NULL*/, double* gstiff /*or NULL*/, ds_stream_t stream);
+
 /* Filtered-noise branch (ABI 44; reference src/ddsp/filtered_noise.py:20-67, FilteredNoise.forward and its autograd): per
  * frame of F samples, L logits -> magnitudes -> a Hann-windowed linear-phase FIR of T = 2 L - 1 taps, applied to a white-noise
  * frame and overlap-added at stride F.  nf = S / F + 1 frames.
