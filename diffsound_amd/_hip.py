@@ -219,6 +219,10 @@ _SIGNATURES = {
     "ds_contact_workspace_bytes": (_I64, [_I, _I, _I, _I]),
     "ds_contact_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P]),
     "ds_contact_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    # multipole series of the modes' exterior fields at listener points: multipole.hip
+    "ds_multipole_workspace_bytes": (_I64, [_I64, _I, _I]),
+    "ds_multipole_fwd": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P, _P]),
+    "ds_multipole_bwd": (_I, [_P, _P, _P, _P, _P, _I64, _I, _I, _P, _I64, _P, _P, _P]),
 }
 # Sliding contact: osc_slide.hip.  A literal of its own: tests/test_osc_refusals_cpu.py holds one refusal table for every
 # ds_osc_* entry of _SIGNATURES and is complete as it stands; the refusals of these three are tabled in

@@ -1073,6 +1073,38 @@ int ds_mode_sample_bwd(const int32_t* tets, int64_t T, int N, int64_t nv, const 
                        const int32_t* elem, const float* L, const float* dir, int64_t P, const double* gout, double* gL,
                        double* gdir, ds_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Radiated sound at a listener (csrc/multipole.hip; still ABI 45, three added symbols): the multipole series of each mode's
+ * exterior field about a centre x0, convention e^{-i w t}, G = e^{ikr} / (4 pi r) as in the boundary elements above.  The
+ * reference has no counterpart.  For mode j (wave number k[j] > 0), d = x - x0, r = |d|, u = d / r:
+ *   out[p, j] = sum_{l=0..L} sum_{n=-l..l} coef[l^2 + l + n, j] h_l(k[j] r_p) Y_{l,n}(u_p),
+ * h_l the spherical Hankel function of the first kind (upward recurrence from h_0 = -i e^{iz} / z), Y_{l,n} the real
+ * orthonormal spherical harmonics: Y_{l,0} = Y_l^0, Y_{l,n>0} = sqrt2 (-1)^n Re Y_l^n, Y_{l,n<0} = sqrt2 (-1)^n Im Y_l^|n|, Y_l^n
+ * with the Condon-Shortley phase; evaluated as solid harmonics by Cartesian recurrences, so a point on the z axis is an
+ * ordinary point.  Everything fp64 on the DEVICE, complex data interleaved (re, im): pts (P x 3), center (3), k (m), coef and
+ * gcoef (N x m) complex with N = (L + 1)^2 and the MODES contiguous (the transpose of a per-mode coefficient list: lane j of a
+ * wavefront owns mode j), out and gout (P x m) complex.  r = 0 and k <= 0 are the caller's to refuse (non-finite results).
+ * ds_multipole_bwd: with <a, b> = sum conj(a) b, gpts (P x 3) = d Re<gout, out> / d pts and gcoef = sum_p gout conj(h_l) Y, the
+ * gradient of Re<gout, out> to (Re coef, Im coef) as a complex number.  Either may be NULL and is then not computed, not both.
+ * gcoef needs work of ds_multipole_workspace_bytes(P, m, L) = 16 min(P, DS_MULTIPOLE_GCOEF_BLOCKS) N m bytes (0 for arguments that
+ * would be refused), 16-byte aligned: per-workgroup partial sums over the points, added in ascending order by a closing
+ * kernel; work may be NULL when gcoef is.  One wavefront per point, no atomics, every output and workspace element has one
+ * owner: the same bits from the same inputs.  Asynchronous on the stream, no allocation, no synchronisation.  Refused
+ * (DS_ERR_ARG, message in ds_last_error()): a null required pointer; P outside 1..DS_MULTIPOLE_MAX_POINTS; m outside
+ * 1..DS_MULTIPOLE_MAX_MODES; L outside 0..DS_MULTIPOLE_MAX_ORDER; both gradient outputs NULL; work_bytes below the query; a
+ * misaligned workspace or operand (complex operands 16 bytes, real ones 8).
+ * ---------------------------------------------------------------------------------------------- */
+#define DS_MULTIPOLE_MAX_ORDER 32        /* L; a real object at 10 kHz has k a of about 18 and needs L in the twenties */
+#define DS_MULTIPOLE_MAX_MODES 512       /* m */
+#define DS_MULTIPOLE_MAX_POINTS 16777216 /* P per call */
+#define DS_MULTIPOLE_GCOEF_BLOCKS 128    /* workgroups (and workspace slabs) of the gcoef reduction */
+int64_t ds_multipole_workspace_bytes(int64_t P, int m, int L);
+int ds_multipole_fwd(const double* pts, const double* center, const double* k, const double* coef, int64_t P, int m, int L,
+                     double* out, ds_stream_t stream);
+int ds_multipole_bwd(const double* gout, const double* pts, const double* center, const double* k, const double* coef, int64_t P,
+                     int m, int L, void* work /*or NULL with gcoef*/, int64_t work_bytes, double* gpts /*or NULL*/,
+                     double* gcoef /*or NULL*/, ds_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
