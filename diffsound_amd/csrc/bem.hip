@@ -13,8 +13,9 @@
 // Oosterom-Strackee solid angle) and the smooth remainder (e^{ikr}-1)/(4 pi r) and its n_y derivative use the inner
 // 6-point rule.  A coincident pair has K_ii = 0 exactly (n_y.(x-y) = 0 on a flat face).
 //
-// e^{ikr} is evaluated from the phase in revolutions: t = fract(kr / 2 pi), then the hardware sine / cosine, whose
-// argument is in revolutions, so kr up to ~100 keeps its fp32 accuracy.  No float atomics: every sum has a fixed
+// e^{ikr} is evaluated from the phase in revolutions: t = fract(kr / 2 pi) with the product in two floats, then the
+// hardware sine / cosine, whose argument is in revolutions; up to kr = 100 the entries stay at the level of the same
+// algorithm in fp32 with libm (DESIGN.md "Accuracy").  No float atomics: every sum has a fixed
 // order, the results are bitwise reproducible.
 #include "ds_common.h"
 
@@ -25,7 +26,8 @@ using f4 = __attribute__((ext_vector_type(4))) float;
 constexpr int REC = DS_BEM_FACE_RECORD;  // floats per face record (layout: include/diffsound_hip.h)
 constexpr float NEAR_RATIO = DS_BEM_NEAR_RATIO;
 constexpr float INV4PI = 0.0795774715459476679f;
-constexpr float INV2PI = 0.159154943091895336f;
+constexpr float INV2PI = 0.159154943091895336f;    // fp32(1 / 2 pi) = 0.15915493667125702
+constexpr float INV2PI_LO = 6.42063832e-9f;         // 1 / 2 pi - INV2PI
 constexpr int ASM_COLS = 256;  // columns per assembly workgroup (one per thread)
 constexpr int ASM_ROWS = 8;    // rows per assembly workgroup
 
@@ -48,10 +50,15 @@ __device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y 
 __device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 __device__ __forceinline__ V3 ld3(const float* p) { return {p[0], p[1], p[2]}; }
 
-// e^{ikr} from the phase in revolutions
+// e^{ikr} from the phase in revolutions.  The product kr / 2 pi is carried in two floats: p, and what p leaves out
+// (the rounding of kr * INV2PI, recovered exactly by the fma, and the part of 1 / 2 pi below its fp32 value).  The
+// fp32 constant alone is 4.0e-8 low, a phase error of 4.0e-8 kr that is the same in every term of a sum, so it does
+// not average out the way the roundings do.  Only the rounding of kr itself is left.
 __device__ __forceinline__ void expikr(float k, float r, float& c, float& s) {
-    float t = k * r * INV2PI;
-    t = t - floorf(t);
+    const float kr = k * r;
+    const float p = kr * INV2PI;
+    const float lo = fmaf(kr, INV2PI_LO, fmaf(kr, INV2PI, -p));
+    const float t = __builtin_amdgcn_fractf(p) + lo;
     s = __builtin_amdgcn_sinf(t);
     c = __builtin_amdgcn_cosf(t);
 }

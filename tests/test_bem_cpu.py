@@ -1,195 +1,19 @@
-"""Helmholtz BEM (diffsound_amd/diffelastic/bem.py, csrc/bem.hip) without a device: the public names, and a NumPy fp64
-restatement of the same formulation and quadrature (6-point rules for regular pairs; for near pairs a 96-point outer
-rule with the static inner part in closed form and the smooth remainder by the inner 6-point rule), checked against
-brute-force integration and against the exact exterior field of a point source.  tests/test_bem_gpu.py checks the
-kernels against this restatement."""
+"""Helmholtz BEM (diffsound_amd/diffelastic/bem.py, csrc/bem.hip) without a device: the public names, and the NumPy fp64
+restatement of the same formulation and quadrature (tests/_bem_ref.py: 6-point rules for regular pairs; for near pairs a
+96-point outer rule with the static inner part in closed form and the smooth remainder by the inner 6-point rule), checked
+against brute-force integration and against the exact exterior field of a point source.  tests/test_bem_gpu.py and
+tests/test_bem_kernels_gpu.py check the kernels against this restatement."""
 import functools
+import os
+import sys
 
 import numpy as np
 import pytest
 
-NEAR_RATIO = 1.75  # DS_BEM_NEAR_RATIO of include/diffsound_hip.h
-INV4PI = 1.0 / (4.0 * np.pi)
-
-_A1, _W1, _A2, _W2 = 0.445948490915965, 0.223381589678011, 0.091576213509771, 0.109951743655322
-
-
-def rule6():
-    """6-point degree-4 rule: barycentrics (6, 3) and weights (6,) summing to 1 (the kernel's order)."""
-    L, W = [], []
-    for a, w in ((_A1, _W1), (_A2, _W2)):
-        b = 1.0 - 2.0 * a
-        for r in range(3):
-            l0 = b if r == 0 else a
-            l1 = b if r == 1 else a
-            L.append((l0, l1, 1.0 - l0 - l1))
-            W.append(w)
-    return np.array(L), np.array(W)
-
-
-def split_rule(levels):
-    """The 6-point rule on each of the 4**levels congruent pieces of the triangle: (l0, l1, l2) on the corners
-    (p0, p1, p2) as the kernel maps them (x = p0 + u e1 + v e2) and weights summing to 1."""
-    s = 2 ** levels
-    L6, W6 = rule6()
-    out, wts = [], []
-    for i in range(s):
-        for j in range(s - i):
-            tris = [((i, j), (i + 1, j), (i, j + 1))]
-            if i + j <= s - 2:
-                tris.append(((i + 1, j), (i + 1, j + 1), (i, j + 1)))
-            for c in tris:
-                c = np.array(c, dtype=np.float64) / s  # (u, v) corners
-                uv = L6 @ c
-                out.append(np.stack([1 - uv[:, 0] - uv[:, 1], uv[:, 0], uv[:, 1]], 1))
-                wts.append(W6 / s ** 2)
-    return np.concatenate(out), np.concatenate(wts)
-
-
-NEAR_OUTER = split_rule(2)  # 16 pieces x 6 points = 96 (the kernel's near-pair outer rule)
-
-
-def geometry(V, F):
-    V = np.asarray(V, dtype=np.float64)
-    F = np.asarray(F, dtype=np.int64)
-    P = V[F]  # (m, 3, 3)
-    cr = np.cross(P[:, 1] - P[:, 0], P[:, 2] - P[:, 0])
-    area = 0.5 * np.linalg.norm(cr, axis=1)
-    L6, W6 = rule6()
-    e = [P[:, 1] - P[:, 0], P[:, 2] - P[:, 0], P[:, 2] - P[:, 1]]
-    return dict(P=P, n=cr / np.linalg.norm(cr, axis=1, keepdims=True), area=area, c=P.mean(1),
-                h=np.sqrt(np.max([(x * x).sum(1) for x in e], axis=0)),
-                q=np.einsum("qa,mad->mqd", L6, P), w=area[:, None] * W6[None, :])
-
-
-def static_integrals(x, P, n):
-    """x (K, 3) points, P (K, 3, 3) triangles, n (K, 3) unit normals -> (int 1/|x-y| dy, int n.(x-y)/|x-y|^3 dy)."""
-    a = P - x[:, None, :]
-    la = np.linalg.norm(a, axis=2)
-    w = -(n * a[:, 0]).sum(1)
-    aw = np.abs(w)
-    acc = np.zeros(len(x))
-    for e in range(3):
-        pa, pb = a[:, e], a[:, (e + 1) % 3]
-        ra, rb = la[:, e], la[:, (e + 1) % 3]
-        d = pb - pa
-        s = d / np.linalg.norm(d, axis=1, keepdims=True)
-        m = np.cross(s, n)
-        t0 = (m * pa).sum(1)
-        sm, sp = (s * pa).sum(1), (s * pb).sum(1)
-        ok = np.abs(t0) > 1e-30
-        with np.errstate(divide="ignore", invalid="ignore"):
-            f = np.where(sp + sm >= 0, np.log((rb + sp) / (ra + sm)), np.log((ra - sm) / (rb - sp)))
-            r02 = t0 * t0 + w * w
-            at = np.arctan(t0 * sp / (r02 + aw * rb)) - np.arctan(t0 * sm / (r02 + aw * ra))
-        acc += np.where(ok, t0 * f - np.where(aw > 0, aw * at, 0.0), 0.0)
-    det = np.einsum("kd,kd->k", a[:, 0], np.cross(a[:, 1], a[:, 2]))
-    den = (la[:, 0] * la[:, 1] * la[:, 2] + (a[:, 0] * a[:, 1]).sum(1) * la[:, 2] + (a[:, 0] * a[:, 2]).sum(1) * la[:, 1]
-           + (a[:, 1] * a[:, 2]).sum(1) * la[:, 0])
-    return acc, -2.0 * np.arctan2(det, den)
-
-
-def kernels(x, y, ny, k):
-    """G and dG/dn_y for broadcastable point arrays (..., 3)."""
-    d = x - y
-    r = np.sqrt((d * d).sum(-1))
-    e = np.exp(1j * k * r)
-    G = e * INV4PI / r
-    dG = (ny * d).sum(-1) * (1 - 1j * k * r) * e * INV4PI / r ** 3
-    return G, dG
-
-
-def near_inner(x, gj, j, k, coincident):
-    """Inner integrals (int G, int dG/dn_y) over faces j (K,) at the points x (K, 3): static part exact, remainder by
-    the 6-point rule.  ``coincident`` (K,) bool: K = 0 there."""
-    s1, dl = static_integrals(x, gj["P"][j], gj["n"][j])
-    d = x[:, None, :] - gj["q"][j]
-    r = np.maximum(np.sqrt((d * d).sum(-1)), 1e-15)
-    e = np.exp(1j * k * r)
-    w = gj["w"][j]
-    v = s1 * INV4PI + (w * (e - 1) * INV4PI / r).sum(1)
-    nd = (d * gj["n"][j][:, None, :]).sum(-1)
-    kk = dl * INV4PI + (w * nd * ((1 - 1j * k * r) * e - 1) * INV4PI / r ** 3).sum(1)
-    return v, np.where(coincident, 0.0, kk)
-
-
-def near_pair(gi, i, gj, j, k, coincident, outer=NEAR_OUTER):
-    """Near-pair entries (V_ij, K_ij) for index arrays i, j (Np,) (or scalars)."""
-    i, j, coincident = np.atleast_1d(i), np.atleast_1d(j), np.atleast_1d(coincident)
-    L, W = outer
-    nq = len(W)
-    x = np.einsum("qa,pad->pqd", L, gi["P"][i]).reshape(-1, 3)
-    v, kk = near_inner(x, gj, np.repeat(j, nq), k, np.repeat(coincident, nq))
-    wx = W[None, :] * gi["area"][i][:, None]
-    return (wx * v.reshape(-1, nq)).sum(1), (wx * kk.reshape(-1, nq)).sum(1)
-
-
-def near_mask(g):
-    d2 = ((g["c"][:, None, :] - g["c"][None, :, :]) ** 2).sum(-1)
-    h = NEAR_RATIO * np.maximum(g["h"][:, None], g["h"][None, :])
-    return d2 < h * h
-
-
-def assemble(g, k, gvec=None, rows=256):
-    """fp64 restatement of ds_bem_assemble: (A = -1/2 M + K, V, rhs = V g, near mask)."""
-    m = len(g["area"])
-    near = near_mask(g)
-    V = np.empty((m, m), complex)
-    K = np.empty((m, m), complex)
-    for i0 in range(0, m, rows):
-        sl = slice(i0, min(m, i0 + rows))
-        x = g["q"][sl][:, None, :, None, :]  # (r, 1, 6, 1, 3)
-        y = g["q"][None, :, None, :, :]      # (1, m, 1, 6, 3)
-        with np.errstate(divide="ignore", invalid="ignore"):  # coincident points: near pairs, replaced below
-            G, dG = kernels(x, y, g["n"][None, :, None, None, :], k)
-            ww = g["w"][sl][:, None, :, None] * g["w"][None, :, None, :]
-            V[sl] = (ww * G).sum((2, 3))
-            K[sl] = (ww * dG).sum((2, 3))
-    I, J = np.nonzero(near)
-    for c0 in range(0, len(I), 512):
-        i, j = I[c0:c0 + 512], J[c0:c0 + 512]
-        V[i, j], K[i, j] = near_pair(g, i, g, j, k, i == j)
-    A = K - 0.5 * np.diag(g["area"])
-    rhs = None if gvec is None else V @ gvec
-    return A, V, rhs, near
-
-
-def potential(g, k, gco, uco, pts):
-    """fp64 restatement of ds_bem_potential: -S g + D u at pts (P, 3)."""
-    x = pts[:, None, None, :]
-    G, dG = kernels(x, g["q"][None], g["n"][None, :, None, :], k)
-    S = (g["w"][None] * G).sum(-1)
-    D = (g["w"][None] * dG).sum(-1)
-    d2 = ((pts[:, None, :] - g["c"][None]) ** 2).sum(-1)
-    p, j = np.nonzero(d2 < (NEAR_RATIO * g["h"][None]) ** 2)
-    if len(p):
-        S[p, j], D[p, j] = near_inner(pts[p], g, j, k, np.zeros(len(p), bool))
-    return -S @ gco + D @ uco
-
-
-# ---------------------------------------------------------------------- point-source problem
-def point_source_data(g, k, x0):
-    """g = DP0 projection (face mean, 6-point rule) of dG(., x0)/dn and the exact boundary trace G(., x0)."""
-    d = g["q"] - x0
-    r = np.linalg.norm(d, axis=-1)
-    e = np.exp(1j * k * r)
-    dn = (d * g["n"][:, None, :]).sum(-1) * (1j * k * r - 1) * e * INV4PI / r ** 3
-    gvec = (g["w"] * dn).sum(1) / g["area"]
-    u_ex = (g["w"] * e * INV4PI / r).sum(1) / g["area"]
-    return gvec, u_ex
-
-
-def listener_points(radius):
-    rng = np.random.default_rng(7)
-    dirs = rng.normal(size=(24, 3))
-    dirs /= np.linalg.norm(dirs, axis=1, keepdims=True)
-    return np.concatenate([dirs * radius * s for s in (2.0, 5.0, 10.0)])
-
-
-def exact_field(pts, k, x0):
-    r = np.linalg.norm(pts - x0, axis=1)
-    return np.exp(1j * k * r) * INV4PI / r
-
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _bem_ref import (INV4PI, NEAR_OUTER, NEAR_RATIO, assemble, exact_field, geometry, kernels,  # noqa: E402,F401
+                      listener_points, near_inner, near_mask, near_pair, point_source_data, potential, rule6, split_rule,
+                      static_integrals)
 
 X0 = np.array([0.2, -0.1, 0.25])  # inside the unit sphere
 
