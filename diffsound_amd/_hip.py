@@ -232,7 +232,13 @@ _SIGNATURES_SLIDE = {
     "ds_osc_slide_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
     "ds_osc_slide_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P]),
 }
-EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SLIDE)
+# Listener bank: osc_listen.hip.  A literal of its own for the same reason; refusals in tests/test_osc_listen_cabi_cpu.py.
+_SIGNATURES_LISTEN = {
+    "ds_osc_listen_workspace_bytes": (_I64, [_I, _I, _I, _I, _I, _I]),
+    "ds_osc_listen_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
+    "ds_osc_listen_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P]),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SLIDE) + tuple(_SIGNATURES_LISTEN)
 
 _lib = None
 
@@ -252,7 +258,7 @@ def lib():
         if got != ABI_VERSION:  # a stale build resolves every symbol and would be called with shifted arguments
             raise RuntimeError(f"diffsound_amd: {LIB_PATH} has ABI version {got}, this package needs {ABI_VERSION} - "
                                "rebuild it with `make -C diffsound_amd/csrc`")
-        for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_SLIDE.items()):
+        for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_SLIDE.items(), *_SIGNATURES_LISTEN.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

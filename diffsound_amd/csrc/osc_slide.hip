@@ -41,31 +41,7 @@ using namespace osc_scan;
 
 static_assert(RUN == DS_OSC_SCAN_RUN, "hop is refused unless it is a multiple of the lane's run");
 
-// the two gains of a lane's run (one frame interval) and what turns a sample of the run into its interpolation weight
-struct lane_gain {
-    double g0, g1;  // gain[k], gain[min(k + 1, K - 1)]
-    double sc;      // 1 / hop, 0 where the last frame is held
-    int off;        // the run's first sample - k hop
-
-    __device__ __forceinline__ double theta(int i) const { return (double)(off + i) * sc; }
-    __device__ __forceinline__ double at(int i) const {
-        const double th = theta(i);
-        return (1.0 - th) * g0 + th * g1;
-    }
-};
-
-// tl: the first sample of the lane's run (a multiple of RUN); grow: the K gains of this (clip, mode)
-__device__ __forceinline__ lane_gain load_gain(const float* __restrict__ grow, int K, int hop, double inv_hop, int tl) {
-    const int kk = tl / hop;
-    const bool held = kk >= K - 1;
-    const int k = held ? K - 1 : kk;
-    lane_gain g;
-    g.g0 = (double)grow[k];
-    g.g1 = (double)grow[held ? K - 1 : k + 1];
-    g.sc = held ? 0.0 : inv_hop;
-    g.off = tl - k * hop;
-    return g;
-}
+// (lane_gain / load_gain, the two gains of a lane's run and its interpolation weights: osc_scan.h)
 
 // 1. one wavefront per (clip, mode): bnd[(a m + mm) ntiles + k] = the state entering tile k.  in: (A x ldin), zero from nin
 // on; GAIN: driven by g_m in (the forward), else by in alone (the adjoint on gy: osc_driven.hip's pass).

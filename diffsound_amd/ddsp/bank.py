@@ -1,9 +1,10 @@
-"""The oscillator banks as functions of tensors: four ``torch.autograd.Function`` wrappers, one per kernel family, and their
+"""The oscillator banks as functions of tensors: five ``torch.autograd.Function`` wrappers, one per kernel family, and their
 functional entries.  ``_OscBank`` is the closed-form bank with the force as a causal FIR out of LDS (ds_osc_bank_fwd / _bwd,
 csrc/oscillator.hip), ``_OscBankTV`` the bank with per-sample rates (ds_osc_tv_fwd / _bwd, same file), ``_OscDriven`` the
 recursive resonator under a force of any length, with a force gradient (ds_osc_driven_fwd / _bwd, csrc/osc_driven.hip),
 ``_OscSliding`` the same resonator with an input gain per mode and per sample, a contact that moves while the force acts
-(ds_osc_slide_fwd / _bwd, csrc/osc_slide.hip).
+(ds_osc_slide_fwd / _bwd, csrc/osc_slide.hip), ``_OscListener`` the resonator read out through complex gains per channel, mode
+and frame, a listener that may move (ds_osc_listen_fwd / _bwd, csrc/osc_listen.hip).
 What they share - operand preparation, the optional ``amp`` across save_for_backward, the gradient buffers - is written
 once below; a ``forward`` / ``backward`` holds its entry point, its workspace and its extra gradient."""
 import torch
@@ -12,6 +13,7 @@ from .. import _hip
 
 FIR_MAX_FORCE = 512  # taps the FIR kernels of csrc/oscillator.hip hold in LDS (MAXF)
 SLIDE_HOP_UNIT = 16  # samples per lane of csrc/osc_slide.hip (DS_OSC_SCAN_RUN): the sliding bank's hop is a multiple of it
+LISTEN_MAX_CHANNELS = 16  # DS_OSC_LISTEN_MAX_CHANNELS of csrc/osc_listen.hip
 
 
 def _prepare(dtype, d, w, amp, force):
@@ -184,6 +186,86 @@ class _OscSliding(torch.autograd.Function):
         if ggain is not None:
             ggain = ggain.transpose(1, 2).to(ctx.gain_dtype)
         return gd, gw, gamp, gforce, ggain, None, None, None
+
+
+def _listener_gain_check(hgain, A, m, hop):
+    """The refusals of ``oscillator_bank_listener`` that need no device; returns (hgain as (A, C, m, K), hop)."""
+    if not torch.is_tensor(hgain) or not hgain.is_complex():
+        raise ValueError("listener bank: hgain must be complex (a real gain g is g + 0i)")
+    if hgain.dim() not in (3, 4) or hgain.shape[0] != A or hgain.shape[2] != m or min(hgain.shape) < 1:
+        raise ValueError(f"listener bank: hgain must be ({A}, C, {m}) or ({A}, C, {m}, K), got {tuple(hgain.shape)}")
+    if hgain.shape[1] > LISTEN_MAX_CHANNELS:
+        raise ValueError(f"listener bank: {hgain.shape[1]} channels, at most {LISTEN_MAX_CHANNELS} channels per call")
+    if hgain.dim() == 3:
+        if hop is not None:
+            raise ValueError("listener bank: hop goes with a 4-D hgain (A, C, m, K); a 3-D one is a listener at rest")
+        return hgain.unsqueeze(-1), SLIDE_HOP_UNIT
+    if hop is None or int(hop) != hop or hop <= 0 or int(hop) % SLIDE_HOP_UNIT:
+        raise ValueError(f"listener bank: hop = {hop} is not a positive multiple of {SLIDE_HOP_UNIT}")
+    return hgain, int(hop)
+
+
+class _OscListener(torch.autograd.Function):
+    """The driven bank read out through a complex gain per (channel, mode, frame), y[a,c,t] = sum_m amp Im(H[a,c,m](t) x_m[a,t]),
+    H piecewise linear between the K frames of ``hgain`` (A, C, m, K), ``hop`` samples apart, the last one held
+    (ds_osc_listen_fwd / ds_osc_listen_bwd, csrc/osc_listen.hip).  Gradients for d, w, amp, force and hgain (complex), each
+    computed only where it is needed."""
+
+    @staticmethod
+    def _work(L, A, C, m, S, K, hop, device):
+        nbytes = L.ds_osc_listen_workspace_bytes(A, C, m, S, K, hop)
+        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+    @staticmethod
+    def forward(ctx, d, w, amp, force, hgain, hop, S, sr):
+        d, w, amp, force = _prepare(torch.float64, d, w, amp, force)
+        _hip.require_gpu(hgain)
+        A, nF = force.shape
+        m = d.shape[0]
+        C, K = hgain.shape[1], hgain.shape[3]
+        # the kernels' layout: (A, C, m, K, 2); a gain built as t.conj() carries torch's lazy conjugate bit, which view_as_real refuses
+        h = torch.view_as_real(hgain.detach().to(torch.complex64).resolve_conj().contiguous())
+        L = _hip.lib()
+        work, nbytes = _OscListener._work(L, A, C, m, S, K, hop, force.device)
+        y = torch.empty((A, C, S), dtype=torch.float32, device=force.device)
+        p = _hip.ptr
+        _hip.check(L.ds_osc_listen_fwd(p(d), p(w), p(amp), p(force), p(h), A, C, m, nF, S, K, hop, float(sr), p(work), nbytes,
+                                       p(y), _hip.stream_ptr()), "ds_osc_listen_fwd")
+        _save(ctx, d, w, amp, force, S, sr)
+        ctx.h, ctx.hop, ctx.h_dtype = h, hop, hgain.dtype
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        d, w, amp, force, gy = _restore(ctx, gy)
+        h, hop = ctx.h, ctx.hop
+        A, nF = force.shape
+        m, C, K = d.shape[0], h.shape[1], h.shape[3]
+        L = _hip.lib()
+        work, nbytes = _OscListener._work(L, A, C, m, ctx.S, K, hop, gy.device)
+        gd, gw, gamp = _grad_buffers(d, w, amp)
+        gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
+        gh = torch.empty_like(h) if ctx.needs_input_grad[4] else None
+        p = _hip.ptr
+        _hip.check(L.ds_osc_listen_bwd(p(gy), p(d), p(w), p(amp), p(force), p(h), A, C, m, nF, ctx.S, K, hop, ctx.sr, p(work),
+                                       nbytes, p(gd), p(gw), p(gamp), p(gforce), p(gh), _hip.stream_ptr()),
+                   "ds_osc_listen_bwd")
+        if gh is not None:  # (d loss / d Re h, d loss / d Im h) is the gradient of a real loss as torch keeps it for a complex leaf
+            gh = torch.view_as_complex(gh).to(ctx.h_dtype)
+        return gd, gw, gamp, gforce, gh, None, None, None
+
+
+def oscillator_bank_listener(d, w, amp, force, hgain, hop, sample_num, sr):
+    """The bank heard through complex output gains: ``oscillator_bank``'s operands plus ``hgain``, complex, (A, C, m) - a
+    listener at rest, ``hop`` None - or (A, C, m, K): the gain of every (channel, mode) at K control frames ``hop`` samples
+    apart (``ModalRadiator.listener_path_gains``), linear in between, the last frame held; ``hop`` a positive multiple of 16.
+    Returns (A, C, sample_num): y[a,c,t] = sum_m amp[a,m] Im(H[a,c,m](t) x_m[a,t]), one scan of the modes for all C <= 16
+    channels.  Autograd reaches d, w, amp, force and hgain (a complex gradient).  ValueError before any launch: hgain not
+    complex or of another shape, more than 16 channels, a bad or missing hop."""
+    if force.dim() != 2:
+        raise ValueError(f"listener bank: force must be (A, F), got {tuple(force.shape)}")
+    hgain, hop = _listener_gain_check(hgain, force.shape[0], d.shape[0], hop)
+    return _OscListener.apply(d, w, amp, force, hgain, hop, int(sample_num), float(sr))
 
 
 def oscillator_bank_sliding(d, w, amp, force, gain, hop, sample_num, sr):

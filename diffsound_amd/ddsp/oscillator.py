@@ -6,7 +6,9 @@ kernel (``ds_osc_bank_fwd`` / ``ds_osc_bank_bwd``) wrapped in a ``torch.autograd
 than 512 taps, or one that is itself trained (``train_forces=True``), renders through the recursive-resonator
 kernels (``ds_osc_driven_fwd`` / ``ds_osc_driven_bwd``), which also return the force gradient; a 3-D ``mode_gain``
 (audio_num, K, mode_num) with ``gain_hop`` - a contact that slides while the force acts - renders through the sliding bank
-(``ds_osc_slide_fwd`` / ``ds_osc_slide_bwd``).
+(``ds_osc_slide_fwd`` / ``ds_osc_slide_bwd``); a complex ``listener_gain`` - what each mode sounds like at C listening points,
+``ModalRadiator.listener_gains`` / ``listener_path_gains`` - renders (audio_num, C, sample_num) through the listener bank
+(``ds_osc_listen_fwd`` / ``ds_osc_listen_bwd``).
 The tiny per-mode parameter algebra (softplus-weighted bins, d = (alpha + beta w0^2)/2,
 w = sqrt(w0^2 - d^2)) stays in torch so autograd reaches every learnable leaf exactly as in the
 reference.
@@ -22,8 +24,9 @@ import torch.nn.functional as F
 
 from .. import _hip  # noqa: F401
 from ..diffelastic.material_model import Material, MatSet  # noqa: F401  (re-exported like the reference)
-from .bank import (FIR_MAX_FORCE, SLIDE_HOP_UNIT, _OscBank, _OscBankTV, _OscDriven, _OscSliding,  # noqa: F401
-                   oscillator_bank, oscillator_bank_driven, oscillator_bank_sliding, oscillator_bank_tv)
+from .bank import (FIR_MAX_FORCE, LISTEN_MAX_CHANNELS, SLIDE_HOP_UNIT, _OscBank, _OscBankTV, _OscDriven,  # noqa: F401
+                   _OscListener, _OscSliding, oscillator_bank, oscillator_bank_driven, oscillator_bank_listener,
+                   oscillator_bank_sliding, oscillator_bank_tv)
 from .filtered_noise import (FN_MAX_COEFF, FN_MAX_FRAME, FilteredNoise, _FilteredNoiseFn,  # noqa: F401
                              _filtered_noise_torch)
 from .utils import modifed_sigmoid
@@ -118,9 +121,11 @@ class _BankBase(nn.Module):
             self._force = self._force.to(dev)
         return dev, self._force
 
-    def _render(self, freq_linear, alpha, beta, amp, slide=None):
+    def _render(self, freq_linear, alpha, beta, amp, slide=None, listen=None):
         """freq_linear (m,1) or (m,) any float dtype; alpha/beta python floats or (1,m,1) tensors; amp (A,m,1)|None;
-        slide: None, or the (gain (A, K, m), hop) of ``_sliding`` - the render then goes through the sliding bank."""
+        slide: None, or the (gain (A, K, m), hop) of ``_sliding`` - the render then goes through the sliding bank;
+        listen: None, or the (hgain (A, C, m[, K]), hop) of ``_listening`` - the render then goes through the listener bank
+        and returns (A, C, S)."""
         dev, force = self._force_on_device()
         f = freq_linear.reshape(self.mode_num).to(dev).double()
         w0sq = (f * (2 * np.pi)) ** 2
@@ -135,7 +140,52 @@ class _BankBase(nn.Module):
         a = None if amp is None else amp.reshape(self.audio_num, self.mode_num).to(dev)
         if slide is not None:
             return oscillator_bank_sliding(d, w, a, force, slide[0].to(dev), slide[1], self.sample_num, self.sr)
+        if listen is not None:
+            return oscillator_bank_listener(d, w, a, force, listen[0].to(dev), listen[1], self.sample_num, self.sr)
         return oscillator_bank(d, w, a, force, self.sample_num, self.sr)
+
+    def _listening(self, listener_gain, listener_hop, slide=None, time_varying=False):
+        """None for ``listener_gain`` = None: the path and the bits of a call without the keyword.  Otherwise the pair
+        (hgain, hop) for the listener bank, after the checks that need no device.  ``listener_gain`` is complex: without
+        ``listener_hop`` (C, mode_num) or (audio_num, C, mode_num), a listener at rest; with ``listener_hop`` - the samples
+        between two frames, a positive multiple of 16 - (C, mode_num, K) or (audio_num, C, mode_num, K), a listener that
+        moves (``ModalRadiator.listener_path_gains``).  A gain without the clip axis is shared by every clip.  ValueError:
+        a real gain, another shape, more than 16 channels, a missing or bad hop, a 3-D ``mode_gain`` (a sliding contact
+        heard by a listener that has gains of its own is not rendered here), or a time-varying render."""
+        if listener_gain is None:
+            if listener_hop is not None:
+                raise ValueError("listener_hop goes with a listener_gain")
+            return None
+        A, m = self.audio_num, self.mode_num
+        if not torch.is_tensor(listener_gain) or not listener_gain.is_complex():
+            raise ValueError("listener_gain must be complex (ModalRadiator.listener_gains; a real gain g is g + 0i)")
+        g = listener_gain
+        if listener_hop is None:
+            if g.dim() == 4:
+                raise ValueError(f"a listener_gain with frames ({A}, C, {m}, K) needs listener_hop, the samples between two frames")
+            ok = (g.dim() == 2 and g.shape[1] == m) or (g.dim() == 3 and g.shape[0] == A and g.shape[2] == m)
+            if not ok:
+                raise ValueError(f"listener_gain must be (C, {m}) or ({A}, C, {m}), got {tuple(g.shape)}")
+            if g.dim() == 2:
+                g = g.unsqueeze(0).expand(A, -1, -1)
+        else:
+            ok = (g.dim() == 3 and g.shape[1] == m) or (g.dim() == 4 and g.shape[0] == A and g.shape[2] == m)
+            if not ok:
+                raise ValueError(f"listener_gain with listener_hop must be (C, {m}, K) or ({A}, C, {m}, K), got {tuple(g.shape)}")
+            if int(listener_hop) != listener_hop or listener_hop <= 0 or int(listener_hop) % SLIDE_HOP_UNIT:
+                raise ValueError(f"listener_hop = {listener_hop} is not a positive multiple of {SLIDE_HOP_UNIT}")
+            listener_hop = int(listener_hop)
+            if g.dim() == 3:
+                g = g.unsqueeze(0).expand(A, -1, -1, -1)
+        if min(g.shape) < 1 or g.shape[1] > LISTEN_MAX_CHANNELS:
+            raise ValueError(f"listener_gain: {g.shape[1]} channels, at least 1 and at most {LISTEN_MAX_CHANNELS} channels per call")
+        if slide is not None:
+            raise ValueError("a 3-D mode_gain together with listener_gain - a sliding contact heard by a listener - is not "
+                             "rendered: use a 2-D mode_gain (a strike)")
+        if time_varying:
+            raise ValueError("listener_gain renders through the closed-form bank only: non_linear_rate must be 0 (and "
+                             "forward_curve has no listener form)")
+        return g, listener_hop
 
     def _sliding(self, mode_gain, gain_hop, time_varying=False):
         """None for ``mode_gain`` = None or a 2-D gain (``_with_gain`` takes those).  For a 3-D gain (audio_num, K, mode_num)
@@ -182,10 +232,14 @@ class TraditionalDampedOscillator(_BankBase):
         self.alpha = mat.alpha
         self.beta = mat.beta
 
-    def forward(self, freq_linear, mode_gain=None, gain_hop=None):
+    def forward(self, freq_linear, mode_gain=None, gain_hop=None, listener_gain=None, listener_hop=None):
+        """``listener_gain`` (complex; see ``_listening``) returns (audio_num, C, sample_num), what C listening points hear;
+        a 2-D ``mode_gain`` (a strike) still folds into the amplitudes.  A sliding contact (3-D ``mode_gain``) heard by a
+        moving listener is out of scope: ValueError."""
         slide = self._sliding(mode_gain, gain_hop)
+        listen = self._listening(listener_gain, listener_hop, slide)
         sig = self._render(freq_linear, float(self.alpha), float(self.beta),
-                           None if slide else self._with_gain(None, mode_gain), slide)
+                           None if slide else self._with_gain(None, mode_gain), slide, listen)
         w = self.damped_freq[0, :, 0].double() * (2 * np.pi)
         self.undamped_freq = freq_linear.reshape(1, self.mode_num, 1).to(w.device)
         return sig
@@ -207,10 +261,14 @@ class DampedOscillator(_BankBase):
         # unused by forward(), kept so that the reference's checkpoints load strictly (oscillator.py:78: "just for load")
         self.noise = FilteredNoise(audio_num, 8000)
 
-    def forward(self, freq_linear, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None, gain_hop=None):
+    def forward(self, freq_linear, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None, gain_hop=None, listener_gain=None,
+                listener_hop=None):
+        """``listener_gain`` / ``listener_hop``: as ``TraditionalDampedOscillator.forward`` - (audio_num, C, sample_num); no
+        sliding contact and no non-zero ``non_linear_rate`` with it."""
         slide = self._sliding(mode_gain, gain_hop)
+        listen = self._listening(listener_gain, listener_hop, slide, time_varying=non_linear_rate != 0.0)
         amp = self.amp() if slide else self._with_gain(self.amp(), mode_gain)
-        return self._render(freq_linear, self.alpha(), self.beta(), amp, slide)
+        return self._render(freq_linear, self.alpha(), self.beta(), amp, slide, listen)
 
     def _curve_render(self, freq_linear, damping_curve):
         dev, force = self._force_on_device()
@@ -225,8 +283,11 @@ class DampedOscillator(_BankBase):
         """Damping per mode from ``damping_curve``, unit amplitudes, no normalisation (reference oscillator.py:85-109)."""
         return self._curve_render(freq_linear, damping_curve)
 
-    def forward_curve(self, freq_linear, damping_curve):
-        """As ``early`` with the output peak-normalised per clip (reference oscillator.py:143-176)."""
+    def forward_curve(self, freq_linear, damping_curve, listener_gain=None):
+        """As ``early`` with the output peak-normalised per clip (reference oscillator.py:143-176).  It has no listener
+        form: a ``listener_gain`` is a ValueError."""
+        if listener_gain is not None:
+            raise ValueError("forward_curve has no listener form: render with forward(..., listener_gain=...)")
         sig = self._curve_render(freq_linear, damping_curve)
         return sig / torch.max(torch.abs(sig), dim=1, keepdim=True)[0]
 
@@ -298,18 +359,23 @@ class GTDampedOscillator(_BankBase):
         lbd = (self.freq_linear() * 2 * np.pi) ** 2
         return 0.5 * (self.alpha() + self.beta() * lbd)
 
-    def forward(self, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None, gain_hop=None):
+    def forward(self, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None, gain_hop=None, listener_gain=None,
+                listener_hop=None):
+        """``listener_gain`` / ``listener_hop``: as ``TraditionalDampedOscillator.forward`` - (audio_num, C, sample_num), the
+        noise branch (one signal per clip) added to every channel; ``non_linear_rate`` must be 0 with it."""
         slide = self._sliding(mode_gain, gain_hop, time_varying=non_linear_rate != 0.0)
+        listen = self._listening(listener_gain, listener_hop, slide, time_varying=non_linear_rate != 0.0)
         if non_linear_rate != 0.0:
             sig = self._render_time_varying(non_linear_rate, mode_gain)
         else:
             amp = self.amp() if slide else self._with_gain(self.amp(), mode_gain)
-            sig = self._render(self.freq_linear(), self.alpha(), self.beta(), amp, slide)
+            sig = self._render(self.freq_linear(), self.alpha(), self.beta(), amp, slide, listen)
             fd = self.damped_freq[0, :, 0].double()
             d = self.damping().reshape(-1).double().to(fd.device)
             self.undamped_freq = (torch.sqrt((2 * np.pi * fd) ** 2 + d ** 2) / (2 * np.pi)).float().reshape(1, -1, 1)
         if noise_rate != 0.0:
-            sig = sig + self.noise() * noise_rate
+            noise = self.noise() * noise_rate
+            sig = sig + (noise.unsqueeze(1) if listen else noise)
         return sig
 
     def _render_time_varying(self, rate, mode_gain=None):

@@ -264,6 +264,44 @@ class ModalRadiator:
         """|transfer| (P, m) fp64: the listener's ``mode_gain``, to be multiplied with ``ContactSurface.amplitudes_at``."""
         return self.transfer(points).abs()
 
+    def listener_gains(self, points):
+        """conj(transfer(points)), (P, m) complex128: the oscillator modules' ``listener_gain`` (C = P channels, m modes)
+        for listeners at rest; differentiable in ``points``.
+
+        Why the conjugate.  With the package's e^{-i w t} convention a mode of unit amplitude a(t) = e^{-i w t} is heard at
+        the point as T e^{-i w t}, T = transfer.  The banks keep the mode as the state x ~ e^{+i w t} (z = e^{(-d + i w) / sr})
+        and the dry signal is Im x = sin(w t) = Re(i e^{-i w t}), the real part of the amplitude a = i e^{-i w t}.  The
+        pressure is then Re(T i e^{-i w t}) = -Im(T e^{-i w t}) = Im(conj(T) e^{+i w t}) = Im(conj(T) x): the gain that
+        multiplies the bank's state is conj(T).  (|T| alone, ``gains``, keeps the level and drops the phase.)"""
+        return self.transfer(points).conj()
+
+    def listener_path_gains(self, path):
+        """The listener gains along a path: ``path`` (K, 3) - one listener - or (C, K, 3) - C listeners, e.g. two ears -,
+        the positions at K control frames ``listener_hop`` samples apart.  Returns (C, m, K) complex128 =
+        conj(transfer) at every frame, the oscillator modules' ``listener_gain`` with ``listener_hop``; differentiable in
+        ``path``.
+
+        This is the quasi-static reading of a moving listener: the gain multiplies the modal state sample by sample, and
+        the propagation delay r / c enters only as the phase e^{i k r} of each mode at its own frequency (whose rotation
+        along the path is the Doppler shift) - there is no fractional delay line, so the envelope of a mode is not
+        delayed.  The banks interpolate the gains linearly between frames; between two unit phasors an angle th apart the
+        interpolant dips to cos(th / 2) (0.92 at pi / 4), so a RuntimeWarning names the largest phase step of any mode
+        between two consecutive frames when it exceeds pi / 4: lower the hop (or slow the path down)."""
+        if not isinstance(path, torch.Tensor) or path.dim() not in (2, 3) or path.shape[-1] != 3 or min(path.shape) < 1:
+            raise ValueError("ModalRadiator: path must be a (K, 3) or (C, K, 3) tensor")
+        p3 = path.unsqueeze(0) if path.dim() == 2 else path
+        C, K = p3.shape[0], p3.shape[1]
+        T = self.transfer(p3.reshape(C * K, 3)).reshape(C, K, -1).permute(0, 2, 1)  # (C, m, K)
+        if K > 1:
+            Td = T.detach()
+            step = torch.angle(Td[:, :, 1:] * Td[:, :, :-1].conj()).abs()
+            worst = float(step.max())
+            if worst > math.pi / 4:
+                warnings.warn(f"ModalRadiator.listener_path_gains: a mode's phase turns by {worst:.3g} rad between two "
+                              f"consecutive frames (above pi / 4 = {math.pi / 4:.3g}): the linear interpolation between "
+                              "frames loses level there - lower hop, the samples between two frames", RuntimeWarning)
+        return T.conj()
+
     def field(self, points, chunk=65536):
         """``transfer`` without autograd, ``chunk`` points at a time: for maps."""
         self._outside(points)

@@ -720,6 +720,40 @@ int ds_osc_slide_bwd(const float* gy, const double* d, const double* w, const fl
                      float* gamp /*or NULL*/, float* gforce /*or NULL, A x F*/, float* ggain /*or NULL, A x m x K*/,
                      ds_stream_t stream);
 
+/* Listener bank (still ABI 45, three added symbols): the driven bank above read out through a COMPLEX gain per (channel,
+ * mode, frame) - the listener's half of the chain: a mode that rings as Im x is heard at a point as Im(H x), H the conjugate
+ * of the mode's transfer to that point; channels (two ears) differ in the phase of H, and a listener that moves hears H
+ * rotate (the Doppler shift).  One scan of the modes serves every channel.  The reference has no counterpart.
+ *   x_m[a,t] = z_m (x_m[a,t-1] + force[a,t]),  z_m = exp((-d_m + i w_m) / sr),  x[-1] = 0,  force[t] = 0 for t >= F ;
+ *   H[a,c,m](t) = (1 - th) h[a,c,m,k] + th h[a,c,m,min(k+1, K-1)],  k, th as in ds_osc_slide_fwd (last frame held; th and the
+ *   interpolation in fp64 from the fp32 h) ;
+ *   y[a,c,t] = sum_m amp[a,m] Im(H[a,c,m](t) x_m[a,t]) = sum_m amp (Hr Im x + Hi Re x).
+ * K = 1 is a listener at rest; C = 1, K = 1, h = 1 + 0i gives ds_osc_driven_fwd's y.  Backward, with the complex drive
+ * wdrive_m[a,t] = sum_c gy[a,c,t] H[a,c,m](t) and l[t] = z (l[t+1] + wdrive[t]), l[S] = 0 (no conjugate anywhere):
+ *   gforce[a,j] = sum_m amp Im l_m[a,j] for j < min(F, S), exactly 0 for S <= j < F ;
+ *   gamp[a,m] = sum_c sum_t gy[a,c,t] Im(H x_m[a,t]) ;
+ *   gh[a,c,m,k] = amp sum_t hat_k(t) gy[a,c,t] (Im x_m[a,t], Re x_m[a,t]), hat_k the two interpolation weights (the clamped
+ *   ones land on K-1), exactly (0, 0) for a frame that no sample t < S touches ;
+ *   G_m = sum_a amp sum_t (x_m[t-1] + force[t]) l_m[t] (complex product),  gd = -Im G / sr,  gw = Re G / sr.
+ * h, gh: (A x C x m x K x 2) f32, the frames contiguous, (re, im) innermost, 8-byte aligned.  y, gy: (A x C x S) f32.
+ * 1 <= C <= DS_OSC_LISTEN_MAX_CHANNELS.  hop: a positive multiple of DS_OSC_SCAN_RUN.  amp NULL = 1; gamp is NULL exactly when
+ * amp is; gforce and gh may each be NULL: what is NULL is not computed and does not change the bits of the rest.  Everything
+ * else as ds_osc_driven_fwd / _bwd: dtypes, A <= 65535, work of ds_osc_listen_workspace_bytes(A, C, m, S, K, hop) bytes (0 for
+ * arguments that would be refused), 16-byte aligned, fp64 states, closed-form powers, one fp32 rounding per stored element,
+ * no atomics, the same bits from the same inputs, asynchronous, no allocation.  Refused (DS_ERR_ARG, message in
+ * ds_last_error()), in this order: a null required pointer; A, C, m, F, S or K <= 0; A > 65535; C above
+ * DS_OSC_LISTEN_MAX_CHANNELS; hop <= 0 or no multiple of DS_OSC_SCAN_RUN; sr <= 0; work_bytes below the query; a misaligned
+ * workspace; (backward) gamp without amp or amp without gamp; gd or gw misaligned; a misaligned operand. */
+#define DS_OSC_LISTEN_MAX_CHANNELS 16 /* C: the frame carries of channel c live in lane c; a workgroup carries up to 4 */
+int64_t ds_osc_listen_workspace_bytes(int A, int C, int m, int S, int K, int hop);
+int ds_osc_listen_fwd(const double* d, const double* w, const float* amp, const float* force, const float* h, int A, int C,
+                      int m, int F, int S, int K, int hop, double sr, void* work, int64_t work_bytes, float* y,
+                      ds_stream_t stream);
+int ds_osc_listen_bwd(const float* gy, const double* d, const double* w, const float* amp, const float* force, const float* h,
+                      int A, int C, int m, int F, int S, int K, int hop, double sr, void* work, int64_t work_bytes, double* gd,
+                      double* gw, float* gamp /*NULL with amp*/, float* gforce /*or NULL, A x F*/,
+                      float* gh /*or NULL, A x C x m x K x 2*/, ds_stream_t stream);
+
 /* Contact force (still ABI 45, three added symbols): a Hertz hammer - mass[a] > 0, approach speed vel[a], contact stiffness
  * stiff[a] > 0, exponent p >= 1 (1.5 for Hertz) - coupled to the m modes (d [1/s], w [rad/s, damped]: the banks' pair) of the
  * object it strikes through the modal gains gain[a,i] at the contact point (ds_mode_sample_fwd).  The reference has no

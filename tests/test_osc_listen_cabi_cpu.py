@@ -1,0 +1,137 @@
+"""The listener-bank entry points resolve on a CPU-only box, are declared in the header, bound in _hip and built by the
+Makefile, and refuse bad arguments before any device work."""
+import os
+import re
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+NAMES = ("ds_osc_listen_workspace_bytes", "ds_osc_listen_fwd", "ds_osc_listen_bwd")
+
+
+def _hip_built():
+    from diffsound_amd import _hip
+
+    if not os.path.exists(_hip.LIB_PATH):
+        import __graft_entry__ as g
+
+        g.build()
+    return _hip
+
+
+def test_osc_listen_symbols():
+    _hip = _hip_built()
+    lib = _hip.lib()
+    header = open(os.path.join(ROOT, "include", "diffsound_hip.h")).read()
+    for name in NAMES:
+        assert name in _hip.EXPORTED_SYMBOLS and name in _hip._SIGNATURES_LISTEN and hasattr(lib, name)
+        assert name not in _hip._SIGNATURES
+        assert re.search(r"\b%s\s*\(" % name, header)
+    assert re.search(r"#define DS_OSC_LISTEN_MAX_CHANNELS 16\b", header)
+    assert lib.ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
+    csrc = os.path.join(ROOT, "diffsound_amd", "csrc")
+    assert re.search(r"\bosc_listen\.hip\b", open(os.path.join(csrc, "Makefile")).read())
+    listen, slide, scan = (open(os.path.join(csrc, n)).read() for n in ("osc_listen.hip", "osc_slide.hip", "osc_scan.h"))
+    assert '#include "osc_scan.h"' in listen
+    for helper in ("struct lane_gain", "lane_gain load_gain(", "struct lane_cgain", "lane_cgain load_cgain(",
+                   "cplx run_from_zero(const double* vr, const double* vi, cplx z1)"):
+        assert helper in scan and helper not in slide and helper not in listen, helper
+    assert "atomic" not in listen.replace("No atomics", "").replace("no atomics", "")
+
+
+OK = 1 << 20  # never dereferenced: the checks come first
+GOOD = dict(gy=OK, d=OK, w=OK, amp=OK, force=OK, h=OK, A=2, C=2, m=3, F=5, S=7, K=2, hop=16, sr=32000.0, work=OK, bytes=1 << 16,
+            y=OK, gd=OK, gw=OK, gamp=OK, gforce=OK, gh=OK)
+FWD = ("d", "w", "amp", "force", "h", "A", "C", "m", "F", "S", "K", "hop", "sr", "work", "bytes", "y")
+BWD = ("gy", "d", "w", "amp", "force", "h", "A", "C", "m", "F", "S", "K", "hop", "sr", "work", "bytes", "gd", "gw", "gamp", "gforce",
+       "gh")
+BAD = [(dict(d=None), "null pointer"), (dict(w=None), "null pointer"), (dict(force=None), "null pointer"),
+       (dict(h=None), "null pointer"), (dict(work=None), "null pointer"),
+       (dict(A=0), "empty problem"), (dict(A=-1), "empty problem"), (dict(C=0), "empty problem"), (dict(C=-1), "empty problem"),
+       (dict(m=0), "empty problem"), (dict(F=0), "empty problem"), (dict(S=0), "empty problem"), (dict(S=-3), "empty problem"),
+       (dict(K=0), "empty problem"), (dict(K=-2), "empty problem"),
+       (dict(A=65536), "above 65535"), (dict(C=17), "C = 17 above 16 channels"),
+       (dict(hop=0), "not a positive multiple of 16"), (dict(hop=-16), "not a positive multiple of 16"),
+       (dict(hop=24), "not a positive multiple of 16"), (dict(hop=17), "not a positive multiple of 16"),
+       (dict(sr=0.0), "sr = 0"), (dict(sr=-1.0), "not positive"),
+       (dict(bytes=16 * (2 * 3 + 2 * 3) - 1), "bytes, 192 needed"), (dict(work=OK + 8), "work not 16-byte aligned"),
+       (dict(d=OK + 4), "misaligned operand"), (dict(w=OK + 4), "misaligned operand"), (dict(force=OK + 2), "misaligned operand"),
+       (dict(h=OK + 4), "misaligned operand"), (dict(amp=OK + 1), "misaligned operand")]
+BAD_FWD = [(dict(y=None), "null pointer"), (dict(y=OK + 2), "misaligned operand")]
+BAD_BWD = [(dict(gy=None), "null pointer"), (dict(gd=None), "null pointer"), (dict(gw=None), "null pointer"),
+           (dict(gamp=None), "gamp goes with amp"), (dict(amp=None), "gamp goes with amp"),
+           (dict(gd=OK + 4), "gd or gw not 8-byte aligned"), (dict(gw=OK + 4), "gd or gw not 8-byte aligned"),
+           (dict(gy=OK + 2), "misaligned operand"), (dict(gamp=OK + 2), "misaligned operand"),
+           (dict(gforce=OK + 2), "misaligned operand"), (dict(gh=OK + 4), "misaligned operand")]
+CALLS = [("ds_osc_listen_fwd", FWD, c, t) for c, t in BAD + BAD_FWD] + [("ds_osc_listen_bwd", BWD, c, t) for c, t in BAD + BAD_BWD]
+# the order of the refusals: the earlier reason wins where two are wrong
+ORDER = [(dict(d=None, A=0), "null pointer"), (dict(A=0, C=17), "empty problem"), (dict(A=65536, C=17), "above 65535"),
+         (dict(C=17, hop=24), "above 16 channels"), (dict(hop=24, sr=0.0), "not a positive multiple"), (dict(sr=0.0, bytes=1), "sr = 0"),
+         (dict(bytes=1, work=OK + 8), "192 needed"), (dict(work=OK + 8, d=OK + 4), "work not 16-byte aligned")]
+
+
+def _ids(calls):
+    return [f"{f[7:]}-" + ",".join(f"{k}={v}" for k, v in c.items()) for f, _, c, _ in calls]
+
+
+ORDERED = [(fn, order, c, t) for fn, order in (("ds_osc_listen_fwd", FWD), ("ds_osc_listen_bwd", BWD)) for c, t in ORDER]
+
+
+@pytest.mark.parametrize("fn,order,change,text", CALLS + ORDERED, ids=_ids(CALLS + ORDERED))
+def test_osc_listen_arguments_are_checked_first(fn, order, change, text):
+    """Every host-side refusal: a non-zero status and a message that names the entry point and the reason, in front of any
+    launch (the pointers are fakes that a launch would fault on; the call needs no device)."""
+    lib = _hip_built().lib()
+    args = [dict(GOOD, **change)[k] for k in order]
+    assert getattr(lib, fn)(*args, None) != 0
+    msg = lib.ds_last_error().decode()
+    assert fn in msg and text in msg, msg
+
+
+def test_osc_listen_workspace_query_needs_no_device():
+    lib = _hip_built().lib()
+    assert lib.ds_osc_listen_workspace_bytes(2, 2, 3, 7, 2, 16) == 192
+    assert lib.ds_osc_listen_workspace_bytes(8, 16, 64, 8000, 126, 64) == 16 * (8 * 64 * 8 + 8 * 64)
+    for a in [(0, 2, 3, 7, 2, 16), (2, 0, 3, 7, 2, 16), (2, 17, 3, 7, 2, 16), (2, 2, 0, 7, 2, 16), (2, 2, 3, 0, 2, 16),
+              (2, 2, 3, 7, 0, 16), (2, 2, 3, 7, 2, 0), (2, 2, 3, 7, 2, 8), (2, 2, 3, 7, 2, -16)]:
+        assert lib.ds_osc_listen_workspace_bytes(*a) == 0
+
+
+def test_python_layer_refuses_before_device_work():
+    """The module-level checks of listener_gain need no device: they raise ValueError on a CPU-only box."""
+    import torch
+
+    from diffsound_amd.ddsp.oscillator import DampedOscillator, GTDampedOscillator, TraditionalDampedOscillator
+    from diffsound_amd.diffelastic.material_model import Material, MatSet
+
+    mat = Material(MatSet.Ceramic)
+    force = torch.zeros(2, 8)
+    force[:, 0] = 1
+    f_range = [100.0 * (i + 1) for i in range(8)]
+    freq = torch.linspace(300.0, 900.0, 3).reshape(3, 1)
+    lg = torch.ones(2, 3, dtype=torch.complex64)          # (C, m)
+    mods = [(TraditionalDampedOscillator(force, 2, 3, 64, 32000, mat), (freq,)),
+            (DampedOscillator(force, 2, 3, 64, 32000, f_range, mat), (freq,)),
+            (GTDampedOscillator(force, 2, 3, 64, 32000, f_range, mat), ())]
+    for mod, args in mods:
+        with pytest.raises(ValueError, match="must be complex"):
+            mod(*args, listener_gain=torch.ones(2, 3))
+        with pytest.raises(ValueError, match=r"\(C, 3\) or \(2, C, 3\)"):
+            mod(*args, listener_gain=torch.ones(2, 5, dtype=torch.complex64))
+        with pytest.raises(ValueError, match="needs listener_hop"):
+            mod(*args, listener_gain=torch.ones(2, 2, 3, 4, dtype=torch.complex64))
+        with pytest.raises(ValueError, match=r"\(C, 3, K\) or \(2, C, 3, K\)"):
+            mod(*args, listener_gain=torch.ones(2, 5, 4, dtype=torch.complex64), listener_hop=16)
+        for hop in (24, 0, -16, 8):
+            with pytest.raises(ValueError, match="multiple of 16"):
+                mod(*args, listener_gain=torch.ones(2, 3, 4, dtype=torch.complex64), listener_hop=hop)
+        with pytest.raises(ValueError, match="at most 16 channels"):
+            mod(*args, listener_gain=torch.ones(17, 3, dtype=torch.complex64))
+        with pytest.raises(ValueError, match="listener_hop goes with"):
+            mod(*args, listener_hop=16)
+        with pytest.raises(ValueError, match="sliding contact heard by a listener"):
+            mod(*args, mode_gain=torch.ones(2, 4, 3), gain_hop=16, listener_gain=lg)
+    with pytest.raises(ValueError, match="non_linear_rate must be 0"):
+        mods[2][0](non_linear_rate=0.5, listener_gain=lg)
+    with pytest.raises(ValueError, match="forward_curve"):
+        mods[1][0].forward_curve(freq, lambda f: 0 * f + 5.0, listener_gain=lg)
