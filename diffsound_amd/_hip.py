@@ -238,7 +238,13 @@ _SIGNATURES_LISTEN = {
     "ds_osc_listen_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
     "ds_osc_listen_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P]),
 }
-EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SLIDE) + tuple(_SIGNATURES_LISTEN)
+# Propagation delay: delay.hip.  A literal of its own for the same reason; refusals in tests/test_delay_cabi_cpu.py.
+_SIGNATURES_DELAY = {
+    "ds_delay_workspace_bytes": (_I64, [_I, _I, _I, _I]),
+    "ds_delay_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "ds_delay_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
+}
+EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SLIDE) + tuple(_SIGNATURES_LISTEN) + tuple(_SIGNATURES_DELAY)
 
 _lib = None
 
@@ -258,7 +264,8 @@ def lib():
         if got != ABI_VERSION:  # a stale build resolves every symbol and would be called with shifted arguments
             raise RuntimeError(f"diffsound_amd: {LIB_PATH} has ABI version {got}, this package needs {ABI_VERSION} - "
                                "rebuild it with `make -C diffsound_amd/csrc`")
-        for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_SLIDE.items(), *_SIGNATURES_LISTEN.items()):
+        for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_SLIDE.items(), *_SIGNATURES_LISTEN.items(),
+                                  *_SIGNATURES_DELAY.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

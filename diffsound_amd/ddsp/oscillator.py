@@ -8,7 +8,8 @@ kernels (``ds_osc_driven_fwd`` / ``ds_osc_driven_bwd``), which also return the f
 (audio_num, K, mode_num) with ``gain_hop`` - a contact that slides while the force acts - renders through the sliding bank
 (``ds_osc_slide_fwd`` / ``ds_osc_slide_bwd``); a complex ``listener_gain`` - what each mode sounds like at C listening points,
 ``ModalRadiator.listener_gains`` / ``listener_path_gains`` - renders (audio_num, C, sample_num) through the listener bank
-(``ds_osc_listen_fwd`` / ``ds_osc_listen_bwd``).
+(``ds_osc_listen_fwd`` / ``ds_osc_listen_bwd``); a ``listener_delay`` with it - the propagation delay of every channel,
+``ModalRadiator.listener_path`` - sends the rendered channels through the fractional delay line (``delay.propagate``).
 The tiny per-mode parameter algebra (softplus-weighted bins, d = (alpha + beta w0^2)/2,
 w = sqrt(w0^2 - d^2)) stays in torch so autograd reaches every learnable leaf exactly as in the
 reference.
@@ -27,6 +28,7 @@ from ..diffelastic.material_model import Material, MatSet  # noqa: F401  (re-exp
 from .bank import (FIR_MAX_FORCE, LISTEN_MAX_CHANNELS, SLIDE_HOP_UNIT, _OscBank, _OscBankTV, _OscDriven,  # noqa: F401
                    _OscListener, _OscSliding, oscillator_bank, oscillator_bank_driven, oscillator_bank_listener,
                    oscillator_bank_sliding, oscillator_bank_tv)
+from .delay import propagate
 from .filtered_noise import (FN_MAX_COEFF, FN_MAX_FRAME, FilteredNoise, _FilteredNoiseFn,  # noqa: F401
                              _filtered_noise_torch)
 from .utils import modifed_sigmoid
@@ -187,6 +189,32 @@ class _BankBase(nn.Module):
                              "forward_curve has no listener form)")
         return g, listener_hop
 
+    def _delaying(self, listener_delay, listen):
+        """None for ``listener_delay`` = None: the path and the bits of a call without the keyword.  Otherwise the delay in
+        samples as (audio_num, C, K) for ``delay.propagate``, after the checks that need no device: ``listener_delay`` is
+        (C, K) or (audio_num, C, K) with the C of ``listener_gain`` and, for a listener that moves, its K and its
+        ``listener_hop``; with a gain at rest (no frames) K is 1.  ValueError: no ``listener_gain``, another shape, another K."""
+        if listener_delay is None:
+            return None
+        if listen is None:
+            raise ValueError("listener_delay goes with a listener_gain (ModalRadiator.listener_path returns both)")
+        g = listen[0]
+        A, C, K = self.audio_num, g.shape[1], (g.shape[3] if g.dim() == 4 else 1)
+        t = listener_delay
+        if not torch.is_tensor(t) or not t.is_floating_point() or not (
+                (t.dim() == 2 and t.shape[0] == C) or (t.dim() == 3 and t.shape[0] == A and t.shape[1] == C)):
+            raise ValueError(f"listener_delay must be a floating-point (C, K) or ({A}, C, K) tensor with C = {C}, got "
+                             f"{tuple(t.shape) if torch.is_tensor(t) else type(t).__name__}")
+        if t.shape[-1] != K:
+            raise ValueError(f"listener_delay has {t.shape[-1]} frames, listener_gain has K = {K}: both share listener_hop")
+        return t if t.dim() == 3 else t.unsqueeze(0).expand(A, -1, -1)
+
+    def _propagated(self, sig, delay, listen):
+        """``sig`` (audio_num, C, S) through the delay line; ``delay`` from ``_delaying`` (None: ``sig`` itself)."""
+        if delay is None:
+            return sig
+        return propagate(sig, delay.to(sig.device), listen[1] if listen[1] is not None else SLIDE_HOP_UNIT)
+
     def _sliding(self, mode_gain, gain_hop, time_varying=False):
         """None for ``mode_gain`` = None or a 2-D gain (``_with_gain`` takes those).  For a 3-D gain (audio_num, K, mode_num)
         - the input gains of a contact that moves, one frame every ``gain_hop`` samples
@@ -232,14 +260,18 @@ class TraditionalDampedOscillator(_BankBase):
         self.alpha = mat.alpha
         self.beta = mat.beta
 
-    def forward(self, freq_linear, mode_gain=None, gain_hop=None, listener_gain=None, listener_hop=None):
+    def forward(self, freq_linear, mode_gain=None, gain_hop=None, listener_gain=None, listener_hop=None, listener_delay=None):
         """``listener_gain`` (complex; see ``_listening``) returns (audio_num, C, sample_num), what C listening points hear;
         a 2-D ``mode_gain`` (a strike) still folds into the amplitudes.  A sliding contact (3-D ``mode_gain``) heard by a
-        moving listener is out of scope: ValueError."""
+        moving listener is out of scope: ValueError.  ``listener_delay`` (see ``_delaying``): the propagation delay of
+        every channel in samples, (C, K) or (audio_num, C, K) at the frames of ``listener_gain``
+        (``ModalRadiator.listener_path`` returns the pair) - the rendered channels then pass through ``delay.propagate``."""
         slide = self._sliding(mode_gain, gain_hop)
         listen = self._listening(listener_gain, listener_hop, slide)
+        delay = self._delaying(listener_delay, listen)
         sig = self._render(freq_linear, float(self.alpha), float(self.beta),
                            None if slide else self._with_gain(None, mode_gain), slide, listen)
+        sig = self._propagated(sig, delay, listen)
         w = self.damped_freq[0, :, 0].double() * (2 * np.pi)
         self.undamped_freq = freq_linear.reshape(1, self.mode_num, 1).to(w.device)
         return sig
@@ -262,13 +294,14 @@ class DampedOscillator(_BankBase):
         self.noise = FilteredNoise(audio_num, 8000)
 
     def forward(self, freq_linear, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None, gain_hop=None, listener_gain=None,
-                listener_hop=None):
-        """``listener_gain`` / ``listener_hop``: as ``TraditionalDampedOscillator.forward`` - (audio_num, C, sample_num); no
-        sliding contact and no non-zero ``non_linear_rate`` with it."""
+                listener_hop=None, listener_delay=None):
+        """``listener_gain`` / ``listener_hop`` / ``listener_delay``: as ``TraditionalDampedOscillator.forward`` -
+        (audio_num, C, sample_num); no sliding contact and no non-zero ``non_linear_rate`` with it."""
         slide = self._sliding(mode_gain, gain_hop)
         listen = self._listening(listener_gain, listener_hop, slide, time_varying=non_linear_rate != 0.0)
+        delay = self._delaying(listener_delay, listen)
         amp = self.amp() if slide else self._with_gain(self.amp(), mode_gain)
-        return self._render(freq_linear, self.alpha(), self.beta(), amp, slide, listen)
+        return self._propagated(self._render(freq_linear, self.alpha(), self.beta(), amp, slide, listen), delay, listen)
 
     def _curve_render(self, freq_linear, damping_curve):
         dev, force = self._force_on_device()
@@ -360,11 +393,13 @@ class GTDampedOscillator(_BankBase):
         return 0.5 * (self.alpha() + self.beta() * lbd)
 
     def forward(self, non_linear_rate=0.0, noise_rate=0.0, mode_gain=None, gain_hop=None, listener_gain=None,
-                listener_hop=None):
+                listener_hop=None, listener_delay=None):
         """``listener_gain`` / ``listener_hop``: as ``TraditionalDampedOscillator.forward`` - (audio_num, C, sample_num), the
-        noise branch (one signal per clip) added to every channel; ``non_linear_rate`` must be 0 with it."""
+        noise branch (one signal per clip) added to every channel; ``non_linear_rate`` must be 0 with it.
+        ``listener_delay`` delays the modal channels only: the noise branch is added AFTER propagation and is not delayed."""
         slide = self._sliding(mode_gain, gain_hop, time_varying=non_linear_rate != 0.0)
         listen = self._listening(listener_gain, listener_hop, slide, time_varying=non_linear_rate != 0.0)
+        delay = self._delaying(listener_delay, listen)
         if non_linear_rate != 0.0:
             sig = self._render_time_varying(non_linear_rate, mode_gain)
         else:
@@ -373,6 +408,7 @@ class GTDampedOscillator(_BankBase):
             fd = self.damped_freq[0, :, 0].double()
             d = self.damping().reshape(-1).double().to(fd.device)
             self.undamped_freq = (torch.sqrt((2 * np.pi * fd) ** 2 + d ** 2) / (2 * np.pi)).float().reshape(1, -1, 1)
+            sig = self._propagated(sig, delay, listen)
         if noise_rate != 0.0:
             noise = self.noise() * noise_rate
             sig = sig + (noise.unsqueeze(1) if listen else noise)

@@ -208,6 +208,7 @@ class ModalRadiator:
         self.radius = float(torch.linalg.vector_norm(sv - self.center, dim=1).max())
         lam = obj.eigenvalues.detach().double().reshape(-1).to(dev)
         omega = torch.sqrt(lam.clamp(min=0.0))
+        self.c = float(c)  # the speed of sound: ``listener_path`` turns distances into delays with it
         self.k = omega / c
         if not bool((self.k > 0).all()) or self.k.shape[0] > MAX_MODES:
             raise ValueError("ModalRadiator: every mode needs a positive eigenvalue (no rigid-body modes), at most "
@@ -284,7 +285,7 @@ class ModalRadiator:
         This is the quasi-static reading of a moving listener: the gain multiplies the modal state sample by sample, and
         the propagation delay r / c enters only as the phase e^{i k r} of each mode at its own frequency (whose rotation
         along the path is the Doppler shift) - there is no fractional delay line, so the envelope of a mode is not
-        delayed.  The banks interpolate the gains linearly between frames; between two unit phasors an angle th apart the
+        delayed (``listener_path`` returns the delay beside a gain without the carrier, for the delay line).  The banks interpolate the gains linearly between frames; between two unit phasors an angle th apart the
         interpolant dips to cos(th / 2) (0.92 at pi / 4), so a RuntimeWarning names the largest phase step of any mode
         between two consecutive frames when it exceeds pi / 4: lower the hop (or slow the path down)."""
         if not isinstance(path, torch.Tensor) or path.dim() not in (2, 3) or path.shape[-1] != 3 or min(path.shape) < 1:
@@ -301,6 +302,41 @@ class ModalRadiator:
                               f"consecutive frames (above pi / 4 = {math.pi / 4:.3g}): the linear interpolation between "
                               "frames loses level there - lower hop, the samples between two frames", RuntimeWarning)
         return T.conj()
+
+    def listener_path(self, path, sr):
+        """A moving listener as a gain AND a propagation delay: ``path`` (K, 3) or (C, K, 3) as in ``listener_path_gains``,
+        ``sr`` the sample rate.  Returns (gain (C, m, K) complex128, delay (C, K) fp64 in samples), the oscillator modules'
+        ``listener_gain`` and ``listener_delay`` at one ``listener_hop``:
+
+            delay = sr r / c,  r = |x - center| (formed in torch),     gain = conj(transfer e^{-i k r}).
+
+        The carrier e^{i k r} of each mode is taken out of the gain and the distance goes into the delay line
+        (``ddsp.delay.propagate``) instead, which delays the envelope and the onset as well as the phase: gain and delay
+        together carry what ``listener_path_gains`` put into the phase alone.  Both are differentiable in ``path``.  ``c`` is
+        the speed of sound the radiator was built with (``self.c``).
+
+        What is left in the gain - 1 / r, the directivity, the near-field terms of the series - varies slowly along a path,
+        so the pi / 4 phase-step RuntimeWarning of ``listener_path_gains``, applied here to the stripped gain, fires far
+        later: a hop that turns the full gain by many radians is correct here as long as the delay's own bound holds (a
+        step of at most hop / 2 samples between two frames, a listener below Mach 0.5)."""
+        if not isinstance(path, torch.Tensor) or path.dim() not in (2, 3) or path.shape[-1] != 3 or min(path.shape) < 1:
+            raise ValueError("ModalRadiator: path must be a (K, 3) or (C, K, 3) tensor")
+        if not sr > 0:
+            raise ValueError(f"ModalRadiator.listener_path: sr = {sr!r} is not positive")
+        p3 = path.unsqueeze(0) if path.dim() == 2 else path
+        C, K = p3.shape[0], p3.shape[1]
+        T = self.transfer(p3.reshape(C * K, 3)).reshape(C, K, -1).permute(0, 2, 1)  # (C, m, K)
+        r = torch.linalg.vector_norm(p3.double() - self.center, dim=-1)             # (C, K)
+        kr = self.k[None, :, None] * r[:, None, :]
+        stripped = T * torch.complex(torch.cos(kr), -torch.sin(kr))
+        if K > 1:
+            Td = stripped.detach()
+            worst = float(torch.angle(Td[:, :, 1:] * Td[:, :, :-1].conj()).abs().max())
+            if worst > math.pi / 4:
+                warnings.warn(f"ModalRadiator.listener_path: with the carrier removed a mode's gain still turns by {worst:.3g} rad "
+                              f"between two consecutive frames (above pi / 4 = {math.pi / 4:.3g}): the linear interpolation "
+                              "between frames loses level there - lower hop, the samples between two frames", RuntimeWarning)
+        return stripped.conj(), (float(sr) / self.c) * r
 
     def field(self, points, chunk=65536):
         """``transfer`` without autograd, ``chunk`` points at a time: for maps."""

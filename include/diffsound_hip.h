@@ -754,6 +754,44 @@ int ds_osc_listen_bwd(const float* gy, const double* d, const double* w, const f
                       double* gw, float* gamp /*NULL with amp*/, float* gforce /*or NULL, A x F*/,
                       float* gh /*or NULL, A x C x m x K x 2*/, ds_stream_t stream);
 
+/* Propagation delay (still ABI 45, three added symbols): a time-varying fractional delay line - what a receiver on a path
+ * hears of a source at rest is s(t - r(t) / c): the onset time, the delayed envelope and the Doppler shift at once.  The
+ * listener bank above puts r into the phase of each mode only; this family delays the rendered rows themselves.  The
+ * reference has no counterpart.  Per row b (B rows: clip x channel), all index arithmetic in fp64:
+ *   tau(t) = tau[b,k] + th (tau[b,min(k+1, K-1)] - tau[b,k]),  k, th as in ds_osc_slide_fwd (k = min(t / hop, K-1),
+ *   th = (t - k hop) / hop, th = 0 where t / hop >= K-1: piecewise linear between K frames hop samples apart, the last frame
+ *   held; this is (1 - th) tau_k + th tau_k+1 in the form that returns equal frames exactly) ;
+ *   p(t) = t - tau(t),  n = floor(p),  f = p - n ;
+ *   h(u) = sinc(u) cos^2(pi u / (2 R)) for |u| < R, 0 outside,  R = DS_DELAY_HALF_TAPS,  sinc(u) = sin(pi u) / (pi u) ;
+ *   y[b,t] = sum_{i = -R+1 .. R} h(f - i) s[b, n + i],  s = 0 outside [0, S).
+ * h is not normalised: h(-i) = delta_i, so an integer delay (f = 0) copies s[b,n], bit for bit, and gives exactly 0 where n
+ * lies outside [0, S).  h is C1 everywhere (value and slope vanish at +-R): the derivative to the delay is continuous
+ * where p crosses an integer.  Backward, no conjugate and no approximation:
+ *   gs[b,j] = sum_t gy[b,t] h(p(t) - j) ;
+ *   gtau[b,k] = - sum_t hat_k(t) gy[b,t] sum_j s[b,j] h'(p(t) - j), hat_k the two interpolation weights (the clamped ones
+ *   land on K-1), exactly 0 for a frame that no sample t < S touches.
+ * PRECONDITION (the caller's: tau lives on the device and cannot be checked here): two consecutive frames of a row differ
+ * by at most hop DS_DELAY_MAX_SLOPE - a receiver below Mach 0.5.  Then p rises by 0.5 .. 1.5 per sample, the samples that
+ * reach an input j are one run of at most 4 R + 1, and gs is a gather: no atomics, the same bits from the same inputs.
+ * SAFE FOR EVERY tau: no address is formed from an unchecked p - the range test is made in fp64 before any conversion to
+ * an integer.  A position outside [-R, S + R) yields y = 0; a non-finite tau(t) yields y = NaN and contributes nothing to gs
+ * and gtau, without a memory access; where the slope precondition is violated gs is unspecified (y and gtau are still what
+ * the formulas say) but every search and every index stays inside [0, S).
+ * s, y, gy, gs: (B x S) f32, 4-byte aligned.  tau, gtau: (B x K) f64, in samples, 8-byte aligned.  hop: any positive number of
+ * samples.  1 <= B <= DS_DELAY_MAX_ROWS.  fp32 signal, fp64 weights and accumulation, one fp32 rounding per stored element of
+ * y and gs.  The forward needs no workspace; the backward takes ds_delay_workspace_bytes(B, S, K, hop) bytes (0 for arguments
+ * that would be refused), 16-byte aligned.  gs and gtau may each be NULL: what is NULL is not computed and does not change
+ * the bits of the rest.  Asynchronous on the stream, no allocation.  Refused (DS_ERR_ARG, message in ds_last_error()), in
+ * this order: a null required pointer; B, S or K <= 0; B above DS_DELAY_MAX_ROWS; hop <= 0; (backward) work_bytes below the
+ * query; a misaligned workspace; a misaligned operand. */
+#define DS_DELAY_HALF_TAPS 8    /* R: 2 R = 16 taps per output */
+#define DS_DELAY_MAX_SLOPE 0.5  /* |tau[b,k+1] - tau[b,k]| <= hop DS_DELAY_MAX_SLOPE */
+#define DS_DELAY_MAX_ROWS 65535 /* B: the rows are the launch grid's second axis */
+int64_t ds_delay_workspace_bytes(int B, int S, int K, int hop);
+int ds_delay_fwd(const float* s, const double* tau, int B, int S, int K, int hop, float* y, ds_stream_t stream);
+int ds_delay_bwd(const float* gy, const float* s, const double* tau, int B, int S, int K, int hop, void* work,
+                 int64_t work_bytes, float* gs /*or NULL*/, double* gtau /*or NULL*/, ds_stream_t stream);
+
 /* Contact force (still ABI 45, three added symbols): a Hertz hammer - mass[a] > 0, approach speed vel[a], contact stiffness
  * stiff[a] > 0, exponent p >= 1 (1.5 for Hertz) - coupled to the m modes (d [1/s], w [rad/s, damped]: the banks' pair) of the
  * object it strikes through the modal gains gain[a,i] at the contact point (ds_mode_sample_fwd).  The reference has no
