@@ -244,7 +244,14 @@ _SIGNATURES_DELAY = {
     "ds_delay_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "ds_delay_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
 }
-EXPORTED_SYMBOLS = tuple(_SIGNATURES) + tuple(_SIGNATURES_SLIDE) + tuple(_SIGNATURES_LISTEN) + tuple(_SIGNATURES_DELAY)
+# Recording chain: biquad.hip.  A literal of its own for the same reason; refusals in tests/test_biquad_cabi_cpu.py.
+_SIGNATURES_BIQUAD = {
+    "ds_biquad_workspace_bytes": (_I64, [_I, _I, _I]),
+    "ds_biquad_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "ds_biquad_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
+}
+EXPORTED_SYMBOLS = (tuple(_SIGNATURES) + tuple(_SIGNATURES_SLIDE) + tuple(_SIGNATURES_LISTEN) + tuple(_SIGNATURES_DELAY) +
+                    tuple(_SIGNATURES_BIQUAD))
 
 _lib = None
 
@@ -265,7 +272,7 @@ def lib():
             raise RuntimeError(f"diffsound_amd: {LIB_PATH} has ABI version {got}, this package needs {ABI_VERSION} - "
                                "rebuild it with `make -C diffsound_amd/csrc`")
         for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_SLIDE.items(), *_SIGNATURES_LISTEN.items(),
-                                  *_SIGNATURES_DELAY.items()):
+                                  *_SIGNATURES_DELAY.items(), *_SIGNATURES_BIQUAD.items()):
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

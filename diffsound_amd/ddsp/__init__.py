@@ -1,1 +1,2 @@
+from .biquad import ParametricEQ, biquad_cascade, highpass_biquad, lowpass_biquad  # noqa: F401
 from .contact import HertzHammer, contact_force  # noqa: F401

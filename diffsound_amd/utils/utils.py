@@ -1,11 +1,14 @@
 """Glue helpers the reference's experiment scripts import from ``src.utils.utils`` (reference src/utils/utils.py):
 ``LOBPCG_solver_freq`` (:80-90, on the hot path), ``resample`` (:111-113) and ``plot_spec`` (:164-173) - the two
 names ``experiments/material_sync_train.py:16`` / ``material_real_train.py:16`` need before they can start.
+``highpass_biquad`` / ``lowpass_biquad`` (ddsp/biquad.py) are re-exported here next to ``resample``: they stand in for the
+``torchaudio.functional`` pair that ``material_real_train.py:99-103`` prepares its clips with.
 The COMSOL / audio-folder loaders of that file are outside the path and not provided."""
 import math
 
 import torch
 
+from ..ddsp.biquad import highpass_biquad, lowpass_biquad  # noqa: F401
 from ..lobpcg import lobpcg_func
 
 

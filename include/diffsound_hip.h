@@ -792,6 +792,35 @@ int ds_delay_fwd(const float* s, const double* tau, int B, int S, int K, int hop
 int ds_delay_bwd(const float* gy, const float* s, const double* tau, int B, int S, int K, int hop, void* work,
                  int64_t work_bytes, float* gs /*or NULL*/, double* gtau /*or NULL*/, ds_stream_t stream);
 
+/* Recording chain (still ABI 45, three added symbols): a cascade of S second-order sections (biquads) over B rows of N
+ * samples - the receiver's half of a recorded clip (a microphone, a room, a parametric EQ) and the high-pass that prepares
+ * one.  Per section, zero initial state, a row of sos = (b0 b1 b2 a1 a2) with a0 = 1:
+ *   w[n] = u[n] - a1 w[n-1] - a2 w[n-2] ;   v[n] = b0 w[n] + b1 w[n-1] + b2 w[n-2] ;   section s + 1 reads the v of section s ;
+ *   u of section 0 is x, y is the v of section S - 1.
+ * Backward, the sections in reverse order, g the gradient at a section's output (gy for the last):
+ *   lam[n] = sum_k b_k g[n+k] - a1 lam[n+1] - a2 lam[n+2] (g, lam = 0 from N on): the gradient at the section's input, gx for
+ *   section 0 ;   gb_k = sum_n g[n] w[n-k] ;   ga_k = - sum_n lam[n] w[n-k] ;   gsos row = (gb0 gb1 gb2 ga1 ga2).
+ * x, y, gy, gx: (B x N) f32, 4-byte aligned.  sos: (S x 5) f64 shared by the rows when per_clip = 0, (B x S x 5) when
+ * per_clip = 1; gsos: ALWAYS (B x S x 5) f64 (the caller adds the rows up for shared coefficients); 8-byte aligned.
+ * 1 <= B <= DS_BIQUAD_MAX_ROWS, 1 <= S <= DS_BIQUAD_MAX_SECTIONS.  All arithmetic in fp64; only y and gx are rounded to fp32,
+ * once.  One wavefront a row walks it in tiles of 64 DS_OSC_SCAN_RUN samples, all sections on a tile before the next is
+ * loaded, the lanes joined by a shuffle scan with powers of the companion matrix [[-a1, -a2], [1, 0]] formed by repeated
+ * squaring (no case split on the kind of poles).  The forward needs no workspace.  The backward runs the forward again and
+ * keeps every section's w: ds_biquad_workspace_bytes(B, N, S) = 8 B S N bytes (0 for arguments that would be refused),
+ * 16-byte aligned.  The coefficient sums are added lane by lane over the tiles and joined by one butterfly: no atomics, the
+ * same bits from the same inputs.  No workgroup waits for another.  Asynchronous on the stream, no allocation.
+ * SAFE FOR EVERY sos: no index and no trip count depends on the data.  Unstable or non-finite coefficients yield inf or
+ * NaN in the outputs and nothing else (stability - |a2| < 1 and |a1| < 1 + a2 - is the caller's to check).
+ * Refused (DS_ERR_ARG, message in ds_last_error()), before any device work, in this order: a null pointer (every pointer is
+ * required); B, N or S <= 0; B above DS_BIQUAD_MAX_ROWS; S above DS_BIQUAD_MAX_SECTIONS; per_clip neither 0 nor 1; a misaligned
+ * operand; (backward) a misaligned workspace; work_bytes below the query. */
+#define DS_BIQUAD_MAX_SECTIONS 16 /* S: powers, carried states and coefficient sums of every section live in LDS */
+#define DS_BIQUAD_MAX_ROWS 65535  /* B */
+int64_t ds_biquad_workspace_bytes(int B, int N, int S);
+int ds_biquad_fwd(const float* x, const double* sos, int per_clip, int B, int N, int S, float* y, ds_stream_t stream);
+int ds_biquad_bwd(const float* gy, const float* x, const double* sos, int per_clip, int B, int N, int S, void* work,
+                  int64_t work_bytes, float* gx, double* gsos, ds_stream_t stream);
+
 /* Contact force (still ABI 45, three added symbols): a Hertz hammer - mass[a] > 0, approach speed vel[a], contact stiffness
  * stiff[a] > 0, exponent p >= 1 (1.5 for Hertz) - coupled to the m modes (d [1/s], w [rad/s, damped]: the banks' pair) of the
  * object it strikes through the modal gains gain[a,i] at the contact point (ds_mode_sample_fwd).  The reference has no
