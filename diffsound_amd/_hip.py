@@ -159,7 +159,7 @@ _SIGNATURES = {
     # geometry backward: geomgrad.hip
     "ds_geometry_grad": (_I, [_P, _I64, _I, _I64, _P, _P, _I64, _I, _P, _P, _D, _D, _P, _P, _I, _P, _P, _P]),
     "ds_geometry_grad_tangent": (_I, [_P, _I64, _I, _I64, _P, _P, _I64, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
-    # oscillator family and the pass's read-out: oscillator.hip, readout.hip, osc_driven.hip, filtered_noise.hip
+    # oscillator family and the pass's read-out: oscillator.hip, readout.hip, osc_driven.hip
     "ds_osc_bank_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),
     "ds_osc_bank_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P, _P, _P, _P]),
     "ds_readout_pass": (_I, [_P, _P, _P, _P, _I, _D, _D, _D, _D, _D, _D, _D, _D, _P, _I, _I, _D, _P, _I, _P, _P, _P, _P, _P, _P]),
@@ -169,6 +169,27 @@ _SIGNATURES = {
     "ds_osc_driven_workspace_bytes": (_I64, [_I, _I, _I]),
     "ds_osc_driven_fwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
     "ds_osc_driven_bwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P]),
+    # sliding contact: osc_slide.hip
+    "ds_osc_slide_workspace_bytes": (_I64, [_I, _I, _I, _I, _I]),
+    "ds_osc_slide_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
+    "ds_osc_slide_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    # listener bank: osc_listen.hip
+    "ds_osc_listen_workspace_bytes": (_I64, [_I, _I, _I, _I, _I, _I]),
+    "ds_osc_listen_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
+    "ds_osc_listen_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P]),
+    # propagation delay: delay.hip
+    "ds_delay_workspace_bytes": (_I64, [_I, _I, _I, _I]),
+    "ds_delay_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "ds_delay_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
+    # recording chain: biquad.hip
+    "ds_biquad_workspace_bytes": (_I64, [_I, _I, _I]),
+    "ds_biquad_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "ds_biquad_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
+    # Hertz hammer coupled to the modes: contact.hip
+    "ds_contact_workspace_bytes": (_I64, [_I, _I, _I, _I]),
+    "ds_contact_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P]),
+    "ds_contact_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    # filtered noise: filtered_noise.hip
     "ds_filtered_noise_fwd": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _P]),
     "ds_filtered_noise_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),
     # spectral loss head: stft.hip, specpoints.hip
@@ -215,43 +236,12 @@ _SIGNATURES = {
     # mode shapes at points: modesample.hip
     "ds_mode_sample_fwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P]),
     "ds_mode_sample_bwd": (_I, [_P, _I64, _I, _I64, _P, _I64, _I, _P, _P, _P, _I64, _P, _P, _P, _P]),
-    # Hertz hammer coupled to the modes: contact.hip
-    "ds_contact_workspace_bytes": (_I64, [_I, _I, _I, _I]),
-    "ds_contact_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P]),
-    "ds_contact_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     # multipole series of the modes' exterior fields at listener points: multipole.hip
     "ds_multipole_workspace_bytes": (_I64, [_I64, _I, _I]),
     "ds_multipole_fwd": (_I, [_P, _P, _P, _P, _I64, _I, _I, _P, _P]),
     "ds_multipole_bwd": (_I, [_P, _P, _P, _P, _P, _I64, _I, _I, _P, _I64, _P, _P, _P]),
 }
-# Sliding contact: osc_slide.hip.  A literal of its own: tests/test_osc_refusals_cpu.py holds one refusal table for every
-# ds_osc_* entry of _SIGNATURES and is complete as it stands; the refusals of these three are tabled in
-# tests/test_osc_slide_cabi_cpu.py.  Bound, exported and checked against the header like every other entry.
-_SIGNATURES_SLIDE = {
-    "ds_osc_slide_workspace_bytes": (_I64, [_I, _I, _I, _I, _I]),
-    "ds_osc_slide_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
-    "ds_osc_slide_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P]),
-}
-# Listener bank: osc_listen.hip.  A literal of its own for the same reason; refusals in tests/test_osc_listen_cabi_cpu.py.
-_SIGNATURES_LISTEN = {
-    "ds_osc_listen_workspace_bytes": (_I64, [_I, _I, _I, _I, _I, _I]),
-    "ds_osc_listen_fwd": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P]),
-    "ds_osc_listen_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P]),
-}
-# Propagation delay: delay.hip.  A literal of its own for the same reason; refusals in tests/test_delay_cabi_cpu.py.
-_SIGNATURES_DELAY = {
-    "ds_delay_workspace_bytes": (_I64, [_I, _I, _I, _I]),
-    "ds_delay_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "ds_delay_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
-}
-# Recording chain: biquad.hip.  A literal of its own for the same reason; refusals in tests/test_biquad_cabi_cpu.py.
-_SIGNATURES_BIQUAD = {
-    "ds_biquad_workspace_bytes": (_I64, [_I, _I, _I]),
-    "ds_biquad_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
-    "ds_biquad_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
-}
-EXPORTED_SYMBOLS = (tuple(_SIGNATURES) + tuple(_SIGNATURES_SLIDE) + tuple(_SIGNATURES_LISTEN) + tuple(_SIGNATURES_DELAY) +
-                    tuple(_SIGNATURES_BIQUAD))
+EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib = None
 
@@ -271,8 +261,7 @@ def lib():
         if got != ABI_VERSION:  # a stale build resolves every symbol and would be called with shifted arguments
             raise RuntimeError(f"diffsound_amd: {LIB_PATH} has ABI version {got}, this package needs {ABI_VERSION} - "
                                "rebuild it with `make -C diffsound_amd/csrc`")
-        for name, (res, args) in (*_SIGNATURES.items(), *_SIGNATURES_SLIDE.items(), *_SIGNATURES_LISTEN.items(),
-                                  *_SIGNATURES_DELAY.items(), *_SIGNATURES_BIQUAD.items()):
+        for name, (res, args) in _SIGNATURES.items():
             fn = getattr(handle, name)
             fn.restype = res
             fn.argtypes = args

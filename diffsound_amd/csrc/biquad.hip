@@ -233,7 +233,7 @@ __global__ void __launch_bounds__(64)
         }
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+using ds::aligned;
 
 int check_args(const char* fn, bool pointers, int per_clip, int B, int N, int S) {
     DS_REQUIRE(pointers, "%s: null pointer", fn);

@@ -250,7 +250,7 @@ int check_args(const char* fn, bool pointers, int A, int m, int F, int R, double
     return DS_OK;
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+using ds::aligned;
 
 }  // namespace
 

@@ -261,7 +261,7 @@ __global__ void __launch_bounds__(GT)
     gs[(int64_t)b * S + j] = (float)acc;
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+using ds::aligned;
 
 int check_args(const char* fn, bool pointers, int B, int S, int K, int hop) {
     DS_REQUIRE(pointers, "%s: null pointer", fn);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 
 #include "diffsound_hip.h"
@@ -20,6 +21,9 @@ inline int check_hip(hipError_t e, const char* what) {
 inline hipStream_t as_stream(ds_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// p is a multiple of a (a power of two); a null pointer is aligned
+inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // Workgroups are dealt round-robin over the 8 XCDs (blocks b and b+8 share one L2).  Give each
 // XCD a contiguous slice of the logical work list so neighbouring rows share an L2 (bijective for
@@ -73,8 +77,11 @@ struct ProfScope {
         }                                \
     } while (0)
 
-#define DS_LAUNCH_CHECK(name)                                         \
-    do {                                                              \
-        int _rc = ds::check_hip(hipGetLastError(), name " launch");   \
-        if (_rc != DS_OK) return _rc;                                 \
+// the check behind a launch, as a value (for a launch that is the last thing a function or a lambda does) and as a statement
+#define DS_LAUNCHED(name) ds::check_hip(hipGetLastError(), name " launch")
+
+#define DS_LAUNCH_CHECK(name)            \
+    do {                                 \
+        int _rc = DS_LAUNCHED(name);     \
+        if (_rc != DS_OK) return _rc;    \
     } while (0)

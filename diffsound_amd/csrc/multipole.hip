@@ -279,7 +279,7 @@ int check_args(const char* fn, bool pointers, int64_t P, int m, int L) {
     return DS_OK;
 }
 
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+using ds::aligned;
 
 inline int64_t slabs(int64_t P) { return P < DS_MULTIPOLE_GCOEF_BLOCKS ? P : DS_MULTIPOLE_GCOEF_BLOCKS; }
 

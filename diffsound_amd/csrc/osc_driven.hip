@@ -24,24 +24,25 @@
 // mode whose z^TILE underflows to 0 carries nothing across tiles and nothing else happens.  fp64 states, no atomics,
 // nothing of size (A, m, S) in memory.
 #include <algorithm>
-#include <cstdint>
 
-#include "ds_common.h"
+#include "osc_bank.h"
 #include "osc_scan.h"
 
 namespace {
 
-// the lane-scan helpers (cplx, cmul, zpow, from_prev, load_run, run_from_zero, scan_lanes, lane_entry, tile_exit): osc_scan.h
+// the lane-scan helpers (cplx, cmul, zpow, from_prev, load_run, run_from_zero, scan_lanes, lane_entry, tile_exit), the waves'
+// join and the pieces of the mode pass: osc_scan.h
 using namespace osc_scan;
-
-constexpr int RUN = 16;          // samples per lane
-constexpr int TILE = 64 * RUN;   // samples per wavefront pass (tests/_osc_driven_ref.py mirrors both)
-static_assert(RUN == osc_scan::RUN && TILE == osc_scan::TILE, "osc_scan.h scans RUN samples per lane");
+using ds::aligned;
+using osc_bank::ntiles_of;
 
 // 1. one wavefront per (clip, mode): bnd[(a m + mm) ntiles + k] = the state entering tile k.  in: (A x ldin), zero from nin on.
+// The pass of every bank whose drive is a real row (osc_bank::launch_boundary).  The loop stays written out here and in the
+// two kernels that copy it (osc_slide.hip, osc_listen.hip): inside a shared function the compiler rounds the other product of
+// Im(zT carry) before the fused multiply-add, and the states entering the third tile move by an ulp.
 template <bool REV>
 __global__ void __launch_bounds__(64)
-    osc_drv_boundary_kernel(const double* __restrict__ dd, const double* __restrict__ ww, const float* __restrict__ in,
+    osc_boundary_kernel(const double* __restrict__ dd, const double* __restrict__ ww, const float* __restrict__ in,
                             int ldin, int nin, int m, int ntiles, double inv_sr, double2* __restrict__ bnd) {
     const int mm = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
     const int q = REV ? 63 - lane : lane;
@@ -72,7 +73,7 @@ __global__ void __launch_bounds__(256)
     osc_drv_tile_kernel(const double* __restrict__ dd, const double* __restrict__ ww, const float* __restrict__ amp,
                         const float* __restrict__ in, int ldin, int nin, int m, int ntiles, double inv_sr,
                         const double2* __restrict__ bnd, float* __restrict__ out, int ldout, int nout) {
-    __shared__ double s_part[4][64 * (RUN + 1)];  // (a lane's RUN sums padded to RUN + 1: no bank conflicts)
+    __shared__ double s_part[WAVES][PART];
     const int k = blockIdx.x, a = blockIdx.y;
     const int t0 = k * TILE;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -82,7 +83,7 @@ __global__ void __launch_bounds__(256)
     load_run(in + (int64_t)a * ldin, t0, lane, nin, v);
 #pragma unroll
     for (int i = 0; i < RUN; ++i) acc[i] = 0.0;
-    for (int mm = wave; mm < m; mm += 4) {
+    for (int mm = wave; mm < m; mm += WAVES) {
         const double d = dd[mm], w = ww[mm];
         const double am = amp ? (double)amp[(int64_t)a * m + mm] : 1.0;
         const cplx z1 = zpow(d, w, inv_sr, 1), zq = zpow(d, w, inv_sr, RUN * q);
@@ -97,32 +98,24 @@ __global__ void __launch_bounds__(256)
             acc[i] += am * x.i;
         }
     }
-#pragma unroll
-    for (int i = 0; i < RUN; ++i) s_part[wave][lane * (RUN + 1) + i] = acc[i];
-    __syncthreads();
-    const int n = min(TILE, nout - t0);
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const int o = (j / RUN) * (RUN + 1) + (j % RUN);
-        out[(int64_t)a * ldout + t0 + j] = (float)((s_part[0][o] + s_part[1][o]) + (s_part[2][o] + s_part[3][o]));
-    }
+    join_waves(s_part, acc, lane, wave, min(TILE, nout - t0), out + (int64_t)a * ldout + t0);
 }
 
 // 3. one wavefront per (clip, mode): gamp[a, mm] and gpart[a m + mm] = amp sum_t (x[t-1] + f[t]) l[t].  lbnd: the states
-// of l entering every tile (from above), written by osc_drv_boundary_kernel<true> on gy.
+// of l entering every tile (from above), written by osc_boundary_kernel<true> on gy.
 __global__ void __launch_bounds__(64)
     osc_drv_mode_kernel(const float* __restrict__ gy, const double* __restrict__ dd, const double* __restrict__ ww,
                         const float* __restrict__ amp, const float* __restrict__ force, int F, int m, int S, int ntiles,
                         double inv_sr, const double2* __restrict__ lbnd, float* __restrict__ gamp,
                         double2* __restrict__ gpart) {
     const int mm = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
-    const double d = dd[mm], w = ww[mm];
-    const double am = amp ? (double)amp[(int64_t)a * m + mm] : 1.0;
-    const cplx z1 = zpow(d, w, inv_sr, 1), zT = zpow(d, w, inv_sr, TILE);
-    const cplx zq_up = zpow(d, w, inv_sr, RUN * lane), zq_dn = zpow(d, w, inv_sr, RUN * (63 - lane));
+    const int64_t am_at = (int64_t)a * m + mm;
+    const mode_powers p = load_mode(dd, ww, amp, am_at, mm, lane, inv_sr);
+    const cplx z1 = p.z1;
     const int nf = min(F, S);
     const float* frow = force + (int64_t)a * F;
     const float* grow = gy + (int64_t)a * S;
-    const double2* lb = lbnd + ((int64_t)a * m + mm) * ntiles;
+    const double2* lb = lbnd + am_at * ntiles;
     cplx cx = {0.0, 0.0}, G = {0.0, 0.0};
     double ga = 0.0;
     for (int k = 0; k < ntiles; ++k) {
@@ -132,12 +125,12 @@ __global__ void __launch_bounds__(64)
         load_run(grow, t0, lane, S, g);
         cplx ef = {0.0, 0.0};
         if (t0 < nf) ef = run_from_zero<false>(f, z1);
-        const cplx sf = scan_lanes<false>(ef, zq_up, lane);
-        cplx x = lane_entry<false>(sf, cx, zq_up, lane);
-        cx = tile_exit<false>(sf, cx, zT);
-        const cplx sl = scan_lanes<true>(run_from_zero<true>(g, z1), zq_dn, lane);
+        const cplx sf = scan_lanes<false>(ef, p.zq_up, lane);
+        cplx x = lane_entry<false>(sf, cx, p.zq_up, lane);
+        cx = tile_exit<false>(sf, cx, p.zT);
+        const cplx sl = scan_lanes<true>(run_from_zero<true>(g, z1), p.zq_dn, lane);
         const double2 c = lb[k];
-        cplx l = lane_entry<true>(sl, cplx{c.x, c.y}, zq_dn, lane);
+        cplx l = lane_entry<true>(sl, cplx{c.x, c.y}, p.zq_dn, lane);
         cplx u[RUN];
 #pragma unroll
         for (int i = 0; i < RUN; ++i) {
@@ -153,18 +146,12 @@ __global__ void __launch_bounds__(64)
             G.i += t.i;
         }
     }
-    ga = ds::wave_sum(ga);
-    G.r = ds::wave_sum(G.r);
-    G.i = ds::wave_sum(G.i);
-    if (lane == 0) {
-        if (gamp) gamp[(int64_t)a * m + mm] = (float)ga;
-        gpart[(int64_t)a * m + mm] = make_double2(am * G.r, am * G.i);
-    }
+    store_mode(ga, G, p.am, lane, am_at, gamp, gpart);
 }
 
 // gd[mm] = -Im sum_a G / sr, gw[mm] = Re sum_a G / sr, the clips added in order
-__global__ void osc_drv_reduce_kernel(const double2* __restrict__ gpart, int A, int m, double inv_sr,
-                                      double* __restrict__ gd, double* __restrict__ gw) {
+__global__ void osc_reduce_kernel(const double2* __restrict__ gpart, int A, int m, double inv_sr, double* __restrict__ gd,
+                                  double* __restrict__ gw) {
     const int mm = blockIdx.x * blockDim.x + threadIdx.x;
     if (mm >= m) return;
     double gr = 0.0, gi = 0.0;
@@ -178,31 +165,44 @@ __global__ void osc_drv_reduce_kernel(const double2* __restrict__ gpart, int A, 
 }
 
 // gforce[a, j] = 0 for S <= j < F: taps that no output sample hears
-__global__ void osc_drv_zero_tail_kernel(float* __restrict__ gforce, int F, int S) {
+__global__ void osc_zero_tail_kernel(float* __restrict__ gforce, int F, int S) {
     const int j = S + blockIdx.x * blockDim.x + threadIdx.x;
     if (j < F) gforce[(int64_t)blockIdx.y * F + j] = 0.f;
 }
-
-inline int64_t ntiles_of(int S) { return ds::ceil_div(S, TILE); }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // The checks both entry points make before those of their own operands' alignment, in their order; `fn` names the entry point
 int check_args(const char* fn, bool pointers, int A, int m, int F, int S, double sr, const void* work, int64_t work_bytes) {
     DS_REQUIRE(pointers, "%s: null pointer", fn);
     DS_REQUIRE(A > 0 && m > 0 && S > 0 && F > 0 && sr > 0, "%s: empty problem (A %d, m %d, F %d, S %d)", fn, A, m, F, S);
-    DS_REQUIRE(A <= 65535, "%s: A = %d above 65535", fn, A);
-    DS_REQUIRE(work_bytes >= ds_osc_driven_workspace_bytes(A, m, S), "%s: workspace of %lld bytes, %lld needed", fn,
-               (long long)work_bytes, (long long)ds_osc_driven_workspace_bytes(A, m, S));
-    DS_REQUIRE(aligned(work, 16), "%s: work not 16-byte aligned", fn);
-    return DS_OK;
+    if (int rc = osc_bank::check_clips(fn, A)) return rc;
+    return osc_bank::check_work(fn, work, work_bytes, ds_osc_driven_workspace_bytes(A, m, S));
 }
 
 }  // namespace
 
+int osc_bank::launch_boundary(hipStream_t st, bool rev, const double* d, const double* w, const float* in, int ldin, int nin,
+                              int A, int m, int nt, double inv_sr, double2* bnd) {
+    const dim3 grid((unsigned)m, (unsigned)A);
+    if (rev)
+        osc_boundary_kernel<true><<<grid, 64, 0, st>>>(d, w, in, ldin, nin, m, nt, inv_sr, bnd);
+    else
+        osc_boundary_kernel<false><<<grid, 64, 0, st>>>(d, w, in, ldin, nin, m, nt, inv_sr, bnd);
+    return DS_LAUNCHED("osc_boundary_kernel");
+}
+
+int osc_bank::launch_reduce(hipStream_t st, const double2* gpart, int A, int m, double inv_sr, double* gd, double* gw) {
+    osc_reduce_kernel<<<(unsigned)ds::ceil_div(m, 64), 64, 0, st>>>(gpart, A, m, inv_sr, gd, gw);
+    return DS_LAUNCHED("osc_reduce_kernel");
+}
+
+int osc_bank::launch_zero_tail(hipStream_t st, float* gforce, int A, int F, int S) {
+    osc_zero_tail_kernel<<<dim3((unsigned)ds::ceil_div(F - S, 256), (unsigned)A), 256, 0, st>>>(gforce, F, S);
+    return DS_LAUNCHED("osc_zero_tail_kernel");
+}
+
 extern "C" int64_t ds_osc_driven_workspace_bytes(int A, int m, int S) {
     if (A <= 0 || m <= 0 || S <= 0) return 0;
-    return (int64_t)sizeof(double2) * ((int64_t)A * m * ntiles_of(S) + (int64_t)A * m);
+    return osc_bank::workspace_bytes(A, m, S);
 }
 
 extern "C" int ds_osc_driven_fwd(const double* d, const double* w, const float* amp, const float* force, int A, int m,
@@ -215,12 +215,10 @@ extern "C" int ds_osc_driven_fwd(const double* d, const double* w, const float* 
     const int nin = std::min(F, S);
     double2* bnd = static_cast<double2*>(work);
     const double inv_sr = 1.0 / sr;
-    osc_drv_boundary_kernel<false><<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(d, w, force, F, nin, m, nt, inv_sr, bnd);
-    DS_LAUNCH_CHECK("osc_drv_boundary_kernel");
+    if (int rc = osc_bank::launch_boundary(st, false, d, w, force, F, nin, A, m, nt, inv_sr, bnd)) return rc;
     osc_drv_tile_kernel<false><<<dim3((unsigned)nt, (unsigned)A), 256, 0, st>>>(d, w, amp, force, F, nin, m, nt, inv_sr, bnd, y,
                                                                                S, S);
-    DS_LAUNCH_CHECK("osc_drv_tile_kernel");
-    return DS_OK;
+    return DS_LAUNCHED("osc_drv_tile_kernel");
 }
 
 extern "C" int ds_osc_driven_bwd(const float* gy, const double* d, const double* w, const float* amp, const float* force,
@@ -233,25 +231,18 @@ extern "C" int ds_osc_driven_bwd(const float* gy, const double* d, const double*
                    aligned(gforce, 4),
                "ds_osc_driven_bwd: misaligned operand");
     hipStream_t st = ds::as_stream(stream);
-    const int nt = (int)ntiles_of(S);
-    double2* lbnd = static_cast<double2*>(work);
-    double2* gpart = lbnd + (int64_t)A * m * nt;
     const double inv_sr = 1.0 / sr;
-    osc_drv_boundary_kernel<true><<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(d, w, gy, S, S, m, nt, inv_sr, lbnd);
-    DS_LAUNCH_CHECK("osc_drv_boundary_kernel");
-    if (gforce) {
-        osc_drv_tile_kernel<true><<<dim3((unsigned)nt, (unsigned)A), 256, 0, st>>>(d, w, amp, gy, S, S, m, nt, inv_sr, lbnd,
-                                                                                  gforce, F, std::min(F, S));
-        DS_LAUNCH_CHECK("osc_drv_tile_kernel");
-        if (F > S) {
-            osc_drv_zero_tail_kernel<<<dim3((unsigned)ds::ceil_div(F - S, 256), (unsigned)A), 256, 0, st>>>(gforce, F, S);
-            DS_LAUNCH_CHECK("osc_drv_zero_tail_kernel");
-        }
-    }
-    osc_drv_mode_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(gy, d, w, amp, force, F, m, S, nt, inv_sr, lbnd, gamp,
-                                                                     gpart);
-    DS_LAUNCH_CHECK("osc_drv_mode_kernel");
-    osc_drv_reduce_kernel<<<(unsigned)ds::ceil_div(m, 64), 64, 0, st>>>(gpart, A, m, inv_sr, gd, gw);
-    DS_LAUNCH_CHECK("osc_drv_reduce_kernel");
-    return DS_OK;
+    return osc_bank::backward(
+        st, A, m, F, S, inv_sr, work, gd, gw, gforce,
+        [&](int nt, double2* lbnd) { return osc_bank::launch_boundary(st, true, d, w, gy, S, S, A, m, nt, inv_sr, lbnd); },
+        [&](int nt, const double2* lbnd) {
+            osc_drv_tile_kernel<true><<<dim3((unsigned)nt, (unsigned)A), 256, 0, st>>>(d, w, amp, gy, S, S, m, nt, inv_sr, lbnd,
+                                                                                      gforce, F, std::min(F, S));
+            return DS_LAUNCHED("osc_drv_tile_kernel");
+        },
+        [&](int nt, const double2* lbnd, double2* gpart) {
+            osc_drv_mode_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(gy, d, w, amp, force, F, m, S, nt, inv_sr, lbnd, gamp,
+                                                                             gpart);
+            return DS_LAUNCHED("osc_drv_mode_kernel");
+        });
 }

@@ -36,14 +36,15 @@
 //             reduce          the clips added in order.
 // No atomics, nothing of size (A, m, S) in memory, the workspace of the driven bank.
 #include <algorithm>
-#include <cstdint>
 
-#include "ds_common.h"
+#include "osc_bank.h"
 #include "osc_scan.h"
 
 namespace {
 
 using namespace osc_scan;
+using ds::aligned;
+using osc_bank::ntiles_of;
 
 static_assert(RUN == DS_OSC_SCAN_RUN, "hop is refused unless it is a multiple of the lane's run");
 static_assert(DS_OSC_LISTEN_MAX_CHANNELS <= 64, "the frame carries of channel c live in lane c");
@@ -71,53 +72,34 @@ __device__ __forceinline__ void load_drive(const float* __restrict__ gy, const f
     }
 }
 
-// 1. one wavefront per (clip, mode): bnd[(a m + mm) ntiles + k] = the state entering tile k.  REV = false: x, driven by
-// force (A x F, zero from nin on) - osc_driven.hip's pass; REV = true: l, driven by wdrive.
-template <bool REV>
+// 1. one wavefront per (clip, mode): bnd[(a m + mm) ntiles + k] = the state of l entering tile k (from above), l driven by
+// wdrive, which no tile below S is without.  (The forward's boundary pass does not depend on the channel: it is
+// osc_driven.hip's, osc_bank::launch_boundary.)  q, k and the block around the drive are spelled as in that loop (REV = true)
+// ON PURPOSE: a tidier shape may make the compiler round Im(zT carry) the other way, an ulp in the states.
 __global__ void __launch_bounds__(64)
-    osc_lis_boundary_kernel(const double* __restrict__ dd, const double* __restrict__ ww, const float* __restrict__ in, int ldin,
-                            int nin, const float* __restrict__ h, int C, int K, int hop, int m, int ntiles, double inv_sr,
+    osc_lis_boundary_kernel(const double* __restrict__ dd, const double* __restrict__ ww, const float* __restrict__ gy,
+                            const float* __restrict__ h, int C, int K, int hop, int m, int S, int ntiles, double inv_sr,
                             double2* __restrict__ bnd) {
     const int mm = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
-    const int q = REV ? 63 - lane : lane;
+    const int q = 63 - lane;
     const double d = dd[mm], w = ww[mm];
     const cplx z1 = zpow(d, w, inv_sr, 1), zq = zpow(d, w, inv_sr, RUN * q), zT = zpow(d, w, inv_sr, TILE);
     const double inv_hop = 1.0 / (double)hop;
     double2* b = bnd + ((int64_t)a * m + mm) * ntiles;
     cplx carry = {0.0, 0.0};
     for (int kk = 0; kk < ntiles; ++kk) {
-        const int k = REV ? ntiles - 1 - kk : kk;
+        const int k = ntiles - 1 - kk;
         if (lane == 0) b[k] = make_double2(carry.r, carry.i);
         if (kk == ntiles - 1) break;
         const int t0 = k * TILE;
         cplx e;
-        if (REV) {
+        {
             double vr[RUN], vi[RUN];
-            load_drive(in, h, a, mm, C, m, nin, K, hop, inv_hop, t0, lane, vr, vi);
+            load_drive(gy, h, a, mm, C, m, S, K, hop, inv_hop, t0, lane, vr, vi);
             e = run_from_zero<true>(vr, vi, z1);
-        } else {
-            if (t0 >= nin) {  // (wave-uniform) nothing drives this tile
-                carry = cmul(zT, carry);
-                continue;
-            }
-            double v[RUN];
-            load_run(in + (int64_t)a * ldin, t0, lane, nin, v);
-            e = run_from_zero<false>(v, z1);
         }
-        const cplx s = scan_lanes<REV>(e, zq, lane);
-        carry = tile_exit<REV>(s, carry, zT);
-    }
-}
-
-// the four waves' partial sums of a tile joined in the order (0 + 1) + (2 + 3) and stored: n samples from out
-__device__ __forceinline__ void join_waves(double (*s_part)[64 * (RUN + 1)], const double* acc, int lane, int wave, int n,
-                                           float* __restrict__ out) {
-#pragma unroll
-    for (int i = 0; i < RUN; ++i) s_part[wave][lane * (RUN + 1) + i] = acc[i];
-    __syncthreads();
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const int o = (j / RUN) * (RUN + 1) + (j % RUN);
-        out[j] = (float)((s_part[0][o] + s_part[1][o]) + (s_part[2][o] + s_part[3][o]));
+        const cplx s = scan_lanes<true>(e, zq, lane);
+        carry = tile_exit<true>(s, carry, zT);
     }
 }
 
@@ -128,7 +110,7 @@ __global__ void __launch_bounds__(256)
     osc_lis_tile_kernel(const double* __restrict__ dd, const double* __restrict__ ww, const float* __restrict__ amp,
                         const float* __restrict__ force, int F, int nin, const float* __restrict__ h, int C, int K, int hop, int m,
                         int ntiles, double inv_sr, const double2* __restrict__ bnd, float* __restrict__ y, int S) {
-    __shared__ double s_part[4][64 * (RUN + 1)];  // (a lane's RUN sums padded to RUN + 1: no bank conflicts)
+    __shared__ double s_part[WAVES][PART];
     const int k = blockIdx.x, a = blockIdx.y, c0 = blockIdx.z * NC;
     const int t0 = k * TILE;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -140,7 +122,7 @@ __global__ void __launch_bounds__(256)
     for (int j = 0; j < NC; ++j)
 #pragma unroll
         for (int i = 0; i < RUN; ++i) acc[j][i] = 0.0;
-    for (int mm = wave; mm < m; mm += 4) {
+    for (int mm = wave; mm < m; mm += WAVES) {
         const double d = dd[mm], w = ww[mm];
         const double am = amp ? (double)amp[(int64_t)a * m + mm] : 1.0;
         const cplx z1 = zpow(d, w, inv_sr, 1), zq = zpow(d, w, inv_sr, RUN * lane);
@@ -179,7 +161,7 @@ __global__ void __launch_bounds__(256)
                           const float* __restrict__ gy, const float* __restrict__ h, int C, int K, int hop, int m, int S,
                           int ntiles, double inv_sr, const double2* __restrict__ lbnd, float* __restrict__ gforce, int F,
                           int nout) {
-    __shared__ double s_part[4][64 * (RUN + 1)];
+    __shared__ double s_part[WAVES][PART];
     const int k = blockIdx.x, a = blockIdx.y;
     const int t0 = k * TILE;
     if (t0 >= nout) return;  // (uniform over the workgroup) a tile of taps that get no gradient here
@@ -188,7 +170,7 @@ __global__ void __launch_bounds__(256)
     double acc[RUN];
 #pragma unroll
     for (int i = 0; i < RUN; ++i) acc[i] = 0.0;
-    for (int mm = wave; mm < m; mm += 4) {
+    for (int mm = wave; mm < m; mm += WAVES) {
         const double d = dd[mm], w = ww[mm];
         const double am = amp ? (double)amp[(int64_t)a * m + mm] : 1.0;
         const cplx z1 = zpow(d, w, inv_sr, 1), zq = zpow(d, w, inv_sr, RUN * (63 - lane));
@@ -205,46 +187,6 @@ __global__ void __launch_bounds__(256)
     join_waves(s_part, acc, lane, wave, min(TILE, nout - t0), gforce + (int64_t)a * F + t0);
 }
 
-// where the lanes of a tile stand among the frames (osc_sld_mode_kernel's): lane q holds run kt 64 + q, in frame kq
-struct frame_pos {
-    int kq, kn;      // the frame of this lane's run and of the next lane's
-    int s, s0;       // the lane of this tile at which frame kq starts (<= 0: in an earlier tile), and max(s, 0)
-    int k63, kn63;   // kq, kn of lane 63
-};
-
-// The segmented shuffle scan of osc_sld_mode_kernel for one pair of partials: p0, p1 = the (1 - th) and th weighted sums
-// of a lane's run, belonging to frames kq and kq + 1.  Returns P0[kq] + P1[kq - 1] as far as this lane sees them - the
-// frame's value in the lane after which the frame changes.  (c0, c1): the frame that is open at the tile's end; prev1: P1
-// of the frame before the open one; last1: P1 so far of the frame of the last lane.  All four wave-uniform.
-__device__ __forceinline__ double frame_scan(double p0, double p1, const frame_pos& fp, int lane, double& c0, double& c1,
-                                             double& prev1, double& last1) {
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double u0 = __shfl_up(p0, o, 64), u1 = __shfl_up(p1, o, 64);
-        if (lane - o >= fp.s0) {
-            p0 += u0;
-            p1 += u1;
-        }
-    }
-    if (fp.s <= 0) {
-        p0 += c0;
-        p1 += c1;
-    }
-    const double pl = __shfl(p1, max(fp.s - 1, 0), 64);  // the last lane of frame kq - 1, where it is in this tile
-    const double before = fp.s > 0 ? pl : prev1;
-    const double e0 = __shfl(p0, 63, 64), e1 = __shfl(p1, 63, 64), b63 = __shfl(before, 63, 64);
-    last1 = e1;
-    if (fp.kn63 == fp.k63) {
-        c0 = e0;
-        c1 = e1;
-        prev1 = b63;
-    } else {
-        c0 = c1 = 0.0;
-        prev1 = e1;
-    }
-    return p0 + before;
-}
-
 // 4. one wavefront per (clip, mode): gamp[a, mm], gpart[a m + mm] = amp sum_t (x[t-1] + f[t]) l[t] and, where asked for,
 // gh[a, :, mm, :].  lbnd: the states of l entering every tile (from above), written by the boundary pass on wdrive.
 __global__ void __launch_bounds__(64)
@@ -253,15 +195,15 @@ __global__ void __launch_bounds__(64)
                         int C, int m, int S, int K, int hop, int ntiles, double inv_sr, const double2* __restrict__ lbnd,
                         float* __restrict__ gamp, double2* __restrict__ gpart, float* __restrict__ gh) {
     const int mm = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
-    const double d = dd[mm], w = ww[mm];
-    const double am = amp ? (double)amp[(int64_t)a * m + mm] : 1.0;
-    const cplx z1 = zpow(d, w, inv_sr, 1), zT = zpow(d, w, inv_sr, TILE);
-    const cplx zq_up = zpow(d, w, inv_sr, RUN * lane), zq_dn = zpow(d, w, inv_sr, RUN * (63 - lane));
+    const int64_t am_at = (int64_t)a * m + mm;
+    const mode_powers p = load_mode(dd, ww, amp, am_at, mm, lane, inv_sr);
+    const cplx z1 = p.z1;
+    const double am = p.am;
     const int nf = min(F, S);
     const int hr = hop / RUN;  // runs per frame
     const double inv_hop = 1.0 / (double)hop;
     const float* frow = force + (int64_t)a * F;
-    const double2* lb = lbnd + ((int64_t)a * m + mm) * ntiles;
+    const double2* lb = lbnd + am_at * ntiles;
     cplx cx = {0.0, 0.0}, G = {0.0, 0.0};
     double ga = 0.0;
     // the frame carries of channel c, re and im part, in lane c (read with a broadcast, written by that lane alone)
@@ -272,13 +214,9 @@ __global__ void __launch_bounds__(64)
         load_run(frow, t0, lane, nf, f);
         cplx ef = {0.0, 0.0};
         if (t0 < nf) ef = run_from_zero<false>(f, z1);
-        const cplx sf = scan_lanes<false>(ef, zq_up, lane);
-        cplx x = lane_entry<false>(sf, cx, zq_up, lane);
-        cx = tile_exit<false>(sf, cx, zT);
+        cplx x = x_entry(ef, p, lane, cx);
         load_drive(gy, h, a, mm, C, m, S, K, hop, inv_hop, t0, lane, vr, vi);
-        const cplx sl = scan_lanes<true>(run_from_zero<true>(vr, vi, z1), zq_dn, lane);
-        const double2 c = lb[k];
-        cplx l = lane_entry<true>(sl, cplx{c.x, c.y}, zq_dn, lane);
+        cplx l = l_entry(run_from_zero<true>(vr, vi, z1), p, lane, lb[k]);
         cplx u[RUN], xs[RUN];
 #pragma unroll
         for (int i = 0; i < RUN; ++i) {
@@ -293,15 +231,7 @@ __global__ void __launch_bounds__(64)
             G.r += t.r;
             G.i += t.i;
         }
-        frame_pos fp;
-        const int run = k * 64 + lane;
-        fp.kq = min(run / hr, K - 1);
-        fp.kn = min((run + 1) / hr, K - 1);
-        fp.s = fp.kq * hr - k * 64;
-        fp.s0 = max(fp.s, 0);
-        fp.k63 = __shfl(fp.kq, 63, 64);
-        fp.kn63 = __shfl(fp.kn, 63, 64);
-        const bool ends = fp.kn != fp.kq || (k == ntiles - 1 && lane == 63);
+        const frame_pos fp = frame_of(k, lane, hr, K, ntiles);
         for (int cc = 0; cc < C; ++cc) {
             double g[RUN];
             load_run(gy + ((int64_t)a * C + cc) * S, t0, lane, S, g);
@@ -323,7 +253,7 @@ __global__ void __launch_bounds__(64)
                 double b0 = __shfl(c0i, cc, 64), b1 = __shfl(c1i, cc, 64), bp = __shfl(prev1i, cc, 64), bl = 0.0;
                 const double outr = frame_scan(p0r, p1r, fp, lane, a0, a1, ap, al);
                 const double outi = frame_scan(p0i, p1i, fp, lane, b0, b1, bp, bl);
-                if (ends) {
+                if (fp.ends) {
                     float2* ghrow = reinterpret_cast<float2*>(gh) + (((int64_t)a * C + cc) * m + mm) * K;
                     ghrow[fp.kq] = make_float2((float)(am * outr), (float)(am * outi));
                 }
@@ -335,7 +265,7 @@ __global__ void __launch_bounds__(64)
         }
     }
     if (gh) {  // frames past the last tile: the first one hears the th weights of the last tile's last frame, the others nothing
-        const int klast = min((ntiles * 64 - 1) / hr, K - 1);
+        const int klast = last_frame(ntiles, hr, K);
         for (int cc = 0; cc < C; ++cc) {
             float2* ghrow = reinterpret_cast<float2*>(gh) + (((int64_t)a * C + cc) * m + mm) * K;
             const double lr = __shfl(last1r, cc, 64), li = __shfl(last1i, cc, 64);
@@ -343,39 +273,8 @@ __global__ void __launch_bounds__(64)
             for (int kz = klast + 2 + lane; kz < K; kz += 64) ghrow[kz] = make_float2(0.f, 0.f);
         }
     }
-    ga = ds::wave_sum(ga);
-    G.r = ds::wave_sum(G.r);
-    G.i = ds::wave_sum(G.i);
-    if (lane == 0) {
-        if (gamp) gamp[(int64_t)a * m + mm] = (float)ga;
-        gpart[(int64_t)a * m + mm] = make_double2(am * G.r, am * G.i);
-    }
+    store_mode(ga, G, am, lane, am_at, gamp, gpart);
 }
-
-// gd[mm] = -Im sum_a G / sr, gw[mm] = Re sum_a G / sr, the clips added in order
-__global__ void osc_lis_reduce_kernel(const double2* __restrict__ gpart, int A, int m, double inv_sr, double* __restrict__ gd,
-                                      double* __restrict__ gw) {
-    const int mm = blockIdx.x * blockDim.x + threadIdx.x;
-    if (mm >= m) return;
-    double gr = 0.0, gi = 0.0;
-    for (int a = 0; a < A; ++a) {
-        const double2 g = gpart[(int64_t)a * m + mm];
-        gr += g.x;
-        gi += g.y;
-    }
-    gd[mm] = -gi * inv_sr;
-    gw[mm] = gr * inv_sr;
-}
-
-// gforce[a, j] = 0 for S <= j < F: taps that no output sample hears
-__global__ void osc_lis_zero_tail_kernel(float* __restrict__ gforce, int F, int S) {
-    const int j = S + blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < F) gforce[(int64_t)blockIdx.y * F + j] = 0.f;
-}
-
-inline int64_t ntiles_of(int S) { return ds::ceil_div(S, TILE); }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // The checks both entry points make before those of their own operands' alignment, in osc_slide.hip's order; `fn` names the
 // entry point
@@ -384,15 +283,10 @@ int check_args(const char* fn, bool pointers, int A, int C, int m, int F, int S,
     DS_REQUIRE(pointers, "%s: null pointer", fn);
     DS_REQUIRE(A > 0 && C > 0 && m > 0 && S > 0 && F > 0 && K > 0, "%s: empty problem (A %d, C %d, m %d, F %d, S %d, K %d)", fn, A,
                C, m, F, S, K);
-    DS_REQUIRE(A <= 65535, "%s: A = %d above 65535", fn, A);
+    if (int rc = osc_bank::check_clips(fn, A)) return rc;
     DS_REQUIRE(C <= DS_OSC_LISTEN_MAX_CHANNELS, "%s: C = %d above %d channels", fn, C, DS_OSC_LISTEN_MAX_CHANNELS);
-    DS_REQUIRE(hop > 0 && hop % DS_OSC_SCAN_RUN == 0, "%s: hop = %d is not a positive multiple of %d", fn, hop,
-               DS_OSC_SCAN_RUN);
-    DS_REQUIRE(sr > 0, "%s: sr = %g is not positive", fn, sr);
-    DS_REQUIRE(work_bytes >= ds_osc_listen_workspace_bytes(A, C, m, S, K, hop), "%s: workspace of %lld bytes, %lld needed", fn,
-               (long long)work_bytes, (long long)ds_osc_listen_workspace_bytes(A, C, m, S, K, hop));
-    DS_REQUIRE(aligned(work, 16), "%s: work not 16-byte aligned", fn);
-    return DS_OK;
+    if (int rc = osc_bank::check_frames(fn, hop, sr)) return rc;
+    return osc_bank::check_work(fn, work, work_bytes, ds_osc_listen_workspace_bytes(A, C, m, S, K, hop));
 }
 
 template <int NC>
@@ -408,7 +302,7 @@ extern "C" int64_t ds_osc_listen_workspace_bytes(int A, int C, int m, int S, int
     if (A <= 0 || C <= 0 || C > DS_OSC_LISTEN_MAX_CHANNELS || m <= 0 || S <= 0 || K <= 0 || hop <= 0 ||
         hop % DS_OSC_SCAN_RUN != 0)
         return 0;
-    return (int64_t)sizeof(double2) * ((int64_t)A * m * ntiles_of(S) + (int64_t)A * m);
+    return osc_bank::workspace_bytes(A, m, S);
 }
 
 extern "C" int ds_osc_listen_fwd(const double* d, const double* w, const float* amp, const float* force, const float* h, int A,
@@ -423,17 +317,14 @@ extern "C" int ds_osc_listen_fwd(const double* d, const double* w, const float* 
     const int nin = std::min(F, S);
     double2* bnd = static_cast<double2*>(work);
     const double inv_sr = 1.0 / sr;
-    osc_lis_boundary_kernel<false><<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(d, w, force, F, nin, nullptr, C, K, hop, m, nt,
-                                                                                 inv_sr, bnd);
-    DS_LAUNCH_CHECK("osc_lis_boundary_kernel");
+    if (int rc = osc_bank::launch_boundary(st, false, d, w, force, F, nin, A, m, nt, inv_sr, bnd)) return rc;
     if (C == 1)
         launch_tile<1>(st, d, w, amp, force, F, nin, h, A, C, K, hop, m, nt, inv_sr, bnd, y, S);
     else if (C == 2)
         launch_tile<2>(st, d, w, amp, force, F, nin, h, A, C, K, hop, m, nt, inv_sr, bnd, y, S);
     else
         launch_tile<4>(st, d, w, amp, force, F, nin, h, A, C, K, hop, m, nt, inv_sr, bnd, y, S);
-    DS_LAUNCH_CHECK("osc_lis_tile_kernel");
-    return DS_OK;
+    return DS_LAUNCHED("osc_lis_tile_kernel");
 }
 
 extern "C" int ds_osc_listen_bwd(const float* gy, const double* d, const double* w, const float* amp, const float* force,
@@ -449,25 +340,21 @@ extern "C" int ds_osc_listen_bwd(const float* gy, const double* d, const double*
                    aligned(gamp, 4) && aligned(gforce, 4) && aligned(gh, 8),
                "ds_osc_listen_bwd: misaligned operand");
     hipStream_t st = ds::as_stream(stream);
-    const int nt = (int)ntiles_of(S);
-    double2* lbnd = static_cast<double2*>(work);
-    double2* gpart = lbnd + (int64_t)A * m * nt;
     const double inv_sr = 1.0 / sr;
-    osc_lis_boundary_kernel<true><<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(d, w, gy, S, S, h, C, K, hop, m, nt, inv_sr, lbnd);
-    DS_LAUNCH_CHECK("osc_lis_boundary_kernel");
-    if (gforce) {
-        osc_lis_gforce_kernel<<<dim3((unsigned)nt, (unsigned)A), 256, 0, st>>>(d, w, amp, gy, h, C, K, hop, m, S, nt, inv_sr, lbnd,
-                                                                              gforce, F, std::min(F, S));
-        DS_LAUNCH_CHECK("osc_lis_gforce_kernel");
-        if (F > S) {
-            osc_lis_zero_tail_kernel<<<dim3((unsigned)ds::ceil_div(F - S, 256), (unsigned)A), 256, 0, st>>>(gforce, F, S);
-            DS_LAUNCH_CHECK("osc_lis_zero_tail_kernel");
-        }
-    }
-    osc_lis_mode_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(gy, d, w, amp, force, h, F, C, m, S, K, hop, nt, inv_sr, lbnd,
-                                                                     gamp, gpart, gh);
-    DS_LAUNCH_CHECK("osc_lis_mode_kernel");
-    osc_lis_reduce_kernel<<<(unsigned)ds::ceil_div(m, 64), 64, 0, st>>>(gpart, A, m, inv_sr, gd, gw);
-    DS_LAUNCH_CHECK("osc_lis_reduce_kernel");
-    return DS_OK;
+    return osc_bank::backward(
+        st, A, m, F, S, inv_sr, work, gd, gw, gforce,
+        [&](int nt, double2* lbnd) {
+            osc_lis_boundary_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(d, w, gy, h, C, K, hop, m, S, nt, inv_sr, lbnd);
+            return DS_LAUNCHED("osc_lis_boundary_kernel");
+        },
+        [&](int nt, const double2* lbnd) {
+            osc_lis_gforce_kernel<<<dim3((unsigned)nt, (unsigned)A), 256, 0, st>>>(d, w, amp, gy, h, C, K, hop, m, S, nt, inv_sr,
+                                                                                  lbnd, gforce, F, std::min(F, S));
+            return DS_LAUNCHED("osc_lis_gforce_kernel");
+        },
+        [&](int nt, const double2* lbnd, double2* gpart) {
+            osc_lis_mode_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(gy, d, w, amp, force, h, F, C, m, S, K, hop, nt,
+                                                                             inv_sr, lbnd, gamp, gpart, gh);
+            return DS_LAUNCHED("osc_lis_mode_kernel");
+        });
 }

@@ -9,7 +9,10 @@
 namespace osc_scan {
 
 constexpr int RUN = DS_OSC_SCAN_RUN;  // samples per lane (the unit of the sliding bank's hop, include/diffsound_hip.h)
-constexpr int TILE = 64 * RUN;        // samples per wavefront pass
+constexpr int TILE = 64 * RUN;        // samples per wavefront pass (tests/_osc_driven_ref.py mirrors both)
+constexpr int WAVES = 4;              // waves of a tile-pass workgroup, each looping over its modes
+constexpr int PART = 64 * (RUN + 1);  // a wave's partial sums of a tile: a lane's RUN sums padded to RUN + 1 (no bank conflicts)
+static_assert(sizeof(double) * WAVES * PART == 34816, "the tile passes' LDS: __shared__ double s_part[WAVES][PART]");
 
 struct cplx {
     double r, i;
@@ -103,6 +106,62 @@ __device__ __forceinline__ cplx tile_exit(cplx v, cplx carry, cplx zT) {
     return {__shfl(v.r, last, 64) + c.r, __shfl(v.i, last, 64) + c.i};
 }
 
+// the four waves' partial sums of a tile joined in the order (0 + 1) + (2 + 3) and stored: n samples from out
+__device__ __forceinline__ void join_waves(double (*s_part)[PART], const double* acc, int lane, int wave, int n,
+                                           float* __restrict__ out) {
+#pragma unroll
+    for (int i = 0; i < RUN; ++i) s_part[wave][lane * (RUN + 1) + i] = acc[i];
+    __syncthreads();
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        const int o = (j / RUN) * (RUN + 1) + (j % RUN);
+        out[j] = (float)((s_part[0][o] + s_part[1][o]) + (s_part[2][o] + s_part[3][o]));
+    }
+}
+
+// The mode pass (backward), one wavefront per (clip, mode): x up and l down through the tiles, G = sum_t (x[t-1] + in[t]) l[t].
+// What every tile needs of the mode: its amplitude and the powers of z.
+struct mode_powers {
+    double am;
+    cplx z1, zT, zq_up, zq_dn;  // z, z^TILE, z^(RUN lane), z^(RUN (63 - lane))
+};
+
+__device__ __forceinline__ mode_powers load_mode(const double* __restrict__ dd, const double* __restrict__ ww,
+                                                 const float* __restrict__ amp, int64_t am_at, int mm, int lane, double inv_sr) {
+    const double d = dd[mm], w = ww[mm];
+    mode_powers p;
+    p.am = amp ? (double)amp[am_at] : 1.0;
+    p.z1 = zpow(d, w, inv_sr, 1);
+    p.zT = zpow(d, w, inv_sr, TILE);
+    p.zq_up = zpow(d, w, inv_sr, RUN * lane);
+    p.zq_dn = zpow(d, w, inv_sr, RUN * (63 - lane));
+    return p;
+}
+
+// x entering the lane's run of this tile, from the lanes' from-zero end states ef; cx, the state entering the tile, moves on
+__device__ __forceinline__ cplx x_entry(cplx ef, const mode_powers& p, int lane, cplx& cx) {
+    const cplx sf = scan_lanes<false>(ef, p.zq_up, lane);
+    const cplx x = lane_entry<false>(sf, cx, p.zq_up, lane);
+    cx = tile_exit<false>(sf, cx, p.zT);
+    return x;
+}
+
+// l entering the lane's run from above: el as ef, c the tile's entering state as the downward boundary pass left it
+__device__ __forceinline__ cplx l_entry(cplx el, const mode_powers& p, int lane, double2 c) {
+    return lane_entry<true>(scan_lanes<true>(el, p.zq_dn, lane), cplx{c.x, c.y}, p.zq_dn, lane);
+}
+
+// the lanes' sums joined: gamp[at] = sum_t gy Im x (where asked for) and gpart[at] = amp G
+__device__ __forceinline__ void store_mode(double ga, cplx G, double am, int lane, int64_t at, float* __restrict__ gamp,
+                                           double2* __restrict__ gpart) {
+    ga = ds::wave_sum(ga);
+    G.r = ds::wave_sum(G.r);
+    G.i = ds::wave_sum(G.i);
+    if (lane == 0) {
+        if (gamp) gamp[at] = (float)ga;
+        gpart[at] = make_double2(am * G.r, am * G.i);
+    }
+}
+
 // Gains at control frames hop samples apart, piecewise linear in between, the last frame held (osc_slide.hip: input gains;
 // osc_listen.hip: complex output gains).  hop is a multiple of RUN, so a lane's run lies inside ONE frame interval.
 // the two gains of a lane's run (one frame interval) and what turns a sample of the run into its interpolation weight
@@ -157,5 +216,64 @@ __device__ __forceinline__ lane_cgain load_cgain(const float2* __restrict__ hrow
     g.off = tl - k * hop;
     return g;
 }
+
+// where the lanes of a tile stand among the frames: lane q of tile k holds run k 64 + q, which lies in frame
+// kq = min(run / h, K - 1), h = hop / RUN runs per frame
+struct frame_pos {
+    int kq, kn;      // the frame of this lane's run and of the next lane's
+    int s, s0;       // the lane of this tile at which frame kq starts (<= 0: in an earlier tile), and max(s, 0)
+    int k63, kn63;   // kq, kn of lane 63
+    bool ends;       // the frame changes after this lane, or this is the last lane of the last tile: the lane stores frame kq
+};
+
+__device__ __forceinline__ frame_pos frame_of(int k, int lane, int h, int K, int ntiles) {
+    frame_pos fp;
+    const int run = k * 64 + lane;
+    fp.kq = min(run / h, K - 1);
+    fp.kn = min((run + 1) / h, K - 1);
+    fp.s = fp.kq * h - k * 64;
+    fp.s0 = max(fp.s, 0);
+    fp.k63 = __shfl(fp.kq, 63, 64);
+    fp.kn63 = __shfl(fp.kn, 63, 64);
+    fp.ends = fp.kn != fp.kq || (k == ntiles - 1 && lane == 63);
+    return fp;
+}
+
+// The gradient of the frames' gains.  p0, p1 = the (1 - th) and th weighted sums of a lane's run, belonging to frames kq and
+// kq + 1 (p1 = 0 where the last frame is held).  P0[k], P1[k] = the sums over the runs of frame k: a shuffle scan cut at the
+// frames' first lanes adds them inside the tile in a fixed order.  Returns P0[kq] + P1[kq - 1] as far as this lane sees them -
+// the frame's value in the lane after which the frame changes.  (c0, c1): the frame that is open at the tile's end; prev1: P1
+// of the frame before the open one; last1: P1 so far of the frame of the last lane.  All four wave-uniform.
+__device__ __forceinline__ double frame_scan(double p0, double p1, const frame_pos& fp, int lane, double& c0, double& c1,
+                                             double& prev1, double& last1) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const double u0 = __shfl_up(p0, o, 64), u1 = __shfl_up(p1, o, 64);
+        if (lane - o >= fp.s0) {
+            p0 += u0;
+            p1 += u1;
+        }
+    }
+    if (fp.s <= 0) {
+        p0 += c0;
+        p1 += c1;
+    }
+    const double pl = __shfl(p1, max(fp.s - 1, 0), 64);  // the last lane of frame kq - 1, where it is in this tile
+    const double before = fp.s > 0 ? pl : prev1;
+    const double e0 = __shfl(p0, 63, 64), e1 = __shfl(p1, 63, 64), b63 = __shfl(before, 63, 64);
+    last1 = e1;
+    if (fp.kn63 == fp.k63) {
+        c0 = e0;
+        c1 = e1;
+        prev1 = b63;
+    } else {
+        c0 = c1 = 0.0;
+        prev1 = e1;
+    }
+    return p0 + before;
+}
+
+// the frame of the last tile's last run; the frames past it are closed after the walk (klast + 1 gets last1, the others 0)
+__device__ __forceinline__ int last_frame(int ntiles, int h, int K) { return min((ntiles * 64 - 1) / h, K - 1); }
 
 }  // namespace osc_scan

@@ -22,7 +22,7 @@
 // frames contiguous).  Against the driven kernels:
 //   boundary pass (forward)   the per-mode input is g_m f; a tile past the end of the force is still one product by z^TILE.
 //   tile pass (forward)       the lane's v[i] becomes g_i v[i] per mode.
-//   boundary pass on gy       as in osc_driven.hip (GAIN = false below).
+//   boundary pass on gy       osc_driven.hip's own (osc_bank::launch_boundary).
 //   tile pass on gy (gforce)  weights the OUTPUT, acc[i] += am g_i Im l, not the input.
 //   mode pass                 u = x + g f; and ggain: each lane has two partials per tile, the (1 - th) and th weighted sums
 //                             of f Im l over its run; a segmented shuffle scan adds the lanes of a frame in a fixed order,
@@ -30,37 +30,39 @@
 //                             that ends a frame stores it - every frame once.
 // No atomics, nothing of size (A, m, S) in memory, the workspace of the driven bank.
 #include <algorithm>
-#include <cstdint>
 
-#include "ds_common.h"
+#include "osc_bank.h"
 #include "osc_scan.h"
 
 namespace {
 
 using namespace osc_scan;
+using ds::aligned;
+using osc_bank::ntiles_of;
 
 static_assert(RUN == DS_OSC_SCAN_RUN, "hop is refused unless it is a multiple of the lane's run");
 
 // (lane_gain / load_gain, the two gains of a lane's run and its interpolation weights: osc_scan.h)
 
-// 1. one wavefront per (clip, mode): bnd[(a m + mm) ntiles + k] = the state entering tile k.  in: (A x ldin), zero from nin
-// on; GAIN: driven by g_m in (the forward), else by in alone (the adjoint on gy: osc_driven.hip's pass).
-template <bool REV, bool GAIN>
+// 1. one wavefront per (clip, mode): bnd[(a m + mm) ntiles + k] = the state of x entering tile k, x driven by g_m force
+// (force: A x F, zero from nin on).  osc_driven.hip's boundary loop with the gain on its input; the adjoint's pass on gy is
+// that kernel itself (osc_bank::launch_boundary).  q and k are spelled as in that loop (REV = false) ON PURPOSE: this shape
+// compiles to the instructions the outputs were pinned with, and a tidier one may round Im(zT carry) the other way.
 __global__ void __launch_bounds__(64)
     osc_sld_boundary_kernel(const double* __restrict__ dd, const double* __restrict__ ww, const float* __restrict__ in,
                             int ldin, int nin, const float* __restrict__ gain, int K, int hop, int m, int ntiles,
                             double inv_sr, double2* __restrict__ bnd) {
     const int mm = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
-    const int q = REV ? 63 - lane : lane;
+    const int q = lane;
     const double d = dd[mm], w = ww[mm];
     const cplx z1 = zpow(d, w, inv_sr, 1), zq = zpow(d, w, inv_sr, RUN * q), zT = zpow(d, w, inv_sr, TILE);
     const float* row = in + (int64_t)a * ldin;
-    const float* grow = GAIN ? gain + ((int64_t)a * m + mm) * K : nullptr;
+    const float* grow = gain + ((int64_t)a * m + mm) * K;
     const double inv_hop = 1.0 / (double)hop;
     double2* b = bnd + ((int64_t)a * m + mm) * ntiles;
     cplx carry = {0.0, 0.0};
     for (int kk = 0; kk < ntiles; ++kk) {
-        const int k = REV ? ntiles - 1 - kk : kk;
+        const int k = kk;
         if (lane == 0) b[k] = make_double2(carry.r, carry.i);
         if (kk == ntiles - 1) break;
         const int t0 = k * TILE;
@@ -70,13 +72,11 @@ __global__ void __launch_bounds__(64)
         }
         double v[RUN];
         load_run(row, t0, lane, nin, v);
-        if (GAIN) {
-            const lane_gain g = load_gain(grow, K, hop, inv_hop, t0 + lane * RUN);
+        const lane_gain g = load_gain(grow, K, hop, inv_hop, t0 + lane * RUN);
 #pragma unroll
-            for (int i = 0; i < RUN; ++i) v[i] *= g.at(i);
-        }
-        const cplx s = scan_lanes<REV>(run_from_zero<REV>(v, z1), zq, lane);
-        carry = tile_exit<REV>(s, carry, zT);
+        for (int i = 0; i < RUN; ++i) v[i] *= g.at(i);
+        const cplx s = scan_lanes<false>(run_from_zero<false>(v, z1), zq, lane);
+        carry = tile_exit<false>(s, carry, zT);
     }
 }
 
@@ -88,7 +88,7 @@ __global__ void __launch_bounds__(256)
                         const float* __restrict__ in, int ldin, int nin, const float* __restrict__ gain, int K, int hop, int m,
                         int ntiles, double inv_sr, const double2* __restrict__ bnd, float* __restrict__ out, int ldout,
                         int nout) {
-    __shared__ double s_part[4][64 * (RUN + 1)];  // (a lane's RUN sums padded to RUN + 1: no bank conflicts)
+    __shared__ double s_part[WAVES][PART];
     const int k = blockIdx.x, a = blockIdx.y;
     const int t0 = k * TILE;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -99,7 +99,7 @@ __global__ void __launch_bounds__(256)
     load_run(in + (int64_t)a * ldin, t0, lane, nin, v);
 #pragma unroll
     for (int i = 0; i < RUN; ++i) acc[i] = 0.0;
-    for (int mm = wave; mm < m; mm += 4) {
+    for (int mm = wave; mm < m; mm += WAVES) {
         const double d = dd[mm], w = ww[mm];
         const double am = amp ? (double)amp[(int64_t)a * m + mm] : 1.0;
         const cplx z1 = zpow(d, w, inv_sr, 1), zq = zpow(d, w, inv_sr, RUN * q);
@@ -128,45 +128,36 @@ __global__ void __launch_bounds__(256)
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < RUN; ++i) s_part[wave][lane * (RUN + 1) + i] = acc[i];
-    __syncthreads();
-    const int n = min(TILE, nout - t0);
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-        const int o = (j / RUN) * (RUN + 1) + (j % RUN);
-        out[(int64_t)a * ldout + t0 + j] = (float)((s_part[0][o] + s_part[1][o]) + (s_part[2][o] + s_part[3][o]));
-    }
+    join_waves(s_part, acc, lane, wave, min(TILE, nout - t0), out + (int64_t)a * ldout + t0);
 }
 
 // 3. one wavefront per (clip, mode): gamp[a, mm], gpart[a m + mm] = amp sum_t (x[t-1] + g f[t]) l[t] and, where asked for,
 // ggain[a, mm, :].  lbnd: the states of l entering every tile (from above), written by the boundary pass on gy.
 //
-// ggain.  Lane q of tile kt holds run kt 64 + q, which lies in frame kq = min(run / h, K - 1), h = hop / RUN runs per frame.
-// Its partials p0 = sum_i (1 - th_i) f_i Im l_i and p1 = sum_i th_i f_i Im l_i belong to frames kq and kq + 1 (p1 = 0 where
-// the last frame is held).  P0[k], P1[k] = the sums over the runs of frame k: a shuffle scan cut at the frames' first lanes
-// adds them inside the tile, (c0, c1) carry the frame that is open at the tile's end, prev1 = P1 of the frame before the open
-// one, and the lane after which the frame changes (or the last lane of the last tile) stores am (P0[k] + P1[k-1]).
+// ggain.  A lane's partials p0 = sum_i (1 - th_i) f_i Im l_i and p1 = sum_i th_i f_i Im l_i belong to the frame kq of its run
+// and to kq + 1; frame_scan (osc_scan.h) adds the lanes of a frame, (c0, c1, prev1, last1) carry the frame that is open at the
+// tile's end, and the lane after which the frame changes (or the last lane of the last tile) stores am (P0[k] + P1[k-1]).
 __global__ void __launch_bounds__(64)
     osc_sld_mode_kernel(const float* __restrict__ gy, const double* __restrict__ dd, const double* __restrict__ ww,
                         const float* __restrict__ amp, const float* __restrict__ force, const float* __restrict__ gain, int F,
                         int m, int S, int K, int hop, int ntiles, double inv_sr, const double2* __restrict__ lbnd,
                         float* __restrict__ gamp, double2* __restrict__ gpart, float* __restrict__ ggain) {
     const int mm = blockIdx.x, a = blockIdx.y, lane = threadIdx.x;
-    const double d = dd[mm], w = ww[mm];
-    const double am = amp ? (double)amp[(int64_t)a * m + mm] : 1.0;
-    const cplx z1 = zpow(d, w, inv_sr, 1), zT = zpow(d, w, inv_sr, TILE);
-    const cplx zq_up = zpow(d, w, inv_sr, RUN * lane), zq_dn = zpow(d, w, inv_sr, RUN * (63 - lane));
+    const int64_t am_at = (int64_t)a * m + mm;
+    const mode_powers p = load_mode(dd, ww, amp, am_at, mm, lane, inv_sr);
+    const cplx z1 = p.z1;
+    const double am = p.am;
     const int nf = min(F, S);
     const int h = hop / RUN;
     const double inv_hop = 1.0 / (double)hop;
     const float* frow = force + (int64_t)a * F;
     const float* grow = gy + (int64_t)a * S;
-    const float* gnrow = gain + ((int64_t)a * m + mm) * K;
-    float* ggrow = ggain ? ggain + ((int64_t)a * m + mm) * K : nullptr;
-    const double2* lb = lbnd + ((int64_t)a * m + mm) * ntiles;
+    const float* gnrow = gain + am_at * K;
+    float* ggrow = ggain ? ggain + am_at * K : nullptr;
+    const double2* lb = lbnd + am_at * ntiles;
     cplx cx = {0.0, 0.0}, G = {0.0, 0.0};
     double ga = 0.0;
-    double c0 = 0.0, c1 = 0.0, prev1 = 0.0, last1 = 0.0;  // last1: P1 so far of the frame of the last lane
+    double c0 = 0.0, c1 = 0.0, prev1 = 0.0, last1 = 0.0;
     for (int k = 0; k < ntiles; ++k) {
         const int t0 = k * TILE;
         double f[RUN], g[RUN];
@@ -178,12 +169,8 @@ __global__ void __launch_bounds__(64)
 #pragma unroll
             for (int i = 0; i < RUN; ++i) ef = cmul(z1, cplx{ef.r + gn.at(i) * f[i], ef.i});
         }
-        const cplx sf = scan_lanes<false>(ef, zq_up, lane);
-        cplx x = lane_entry<false>(sf, cx, zq_up, lane);
-        cx = tile_exit<false>(sf, cx, zT);
-        const cplx sl = scan_lanes<true>(run_from_zero<true>(g, z1), zq_dn, lane);
-        const double2 c = lb[k];
-        cplx l = lane_entry<true>(sl, cplx{c.x, c.y}, zq_dn, lane);
+        cplx x = x_entry(ef, p, lane, cx);
+        cplx l = l_entry(run_from_zero<true>(g, z1), p, lane, lb[k]);
         cplx u[RUN];
 #pragma unroll
         for (int i = 0; i < RUN; ++i) {
@@ -203,97 +190,34 @@ __global__ void __launch_bounds__(64)
             p1 += th * fl;
         }
         if (ggrow) {  // (wave-uniform)
-            const int run = k * 64 + lane;
-            const int kq = min(run / h, K - 1), kn = min((run + 1) / h, K - 1);
-            const int s = kq * h - k * 64;  // the lane of this tile at which frame kq starts (<= 0: in an earlier tile)
-            const int s0 = max(s, 0);
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const double u0 = __shfl_up(p0, o, 64), u1 = __shfl_up(p1, o, 64);
-                if (lane - o >= s0) {
-                    p0 += u0;
-                    p1 += u1;
-                }
-            }
-            if (s <= 0) {
-                p0 += c0;
-                p1 += c1;
-            }
-            const double pl = __shfl(p1, max(s - 1, 0), 64);  // the last lane of frame kq - 1, where it is in this tile
-            const double before = s > 0 ? pl : prev1;
-            if (kn != kq || (k == ntiles - 1 && lane == 63)) ggrow[kq] = (float)(am * (p0 + before));
-            const int k63 = __shfl(kq, 63, 64), kn63 = __shfl(kn, 63, 64);
-            const double e0 = __shfl(p0, 63, 64), e1 = __shfl(p1, 63, 64), b63 = __shfl(before, 63, 64);
-            last1 = e1;
-            if (kn63 == k63) {
-                c0 = e0;
-                c1 = e1;
-                prev1 = b63;
-            } else {
-                c0 = c1 = 0.0;
-                prev1 = e1;
-            }
+            const frame_pos fp = frame_of(k, lane, h, K, ntiles);
+            const double out = frame_scan(p0, p1, fp, lane, c0, c1, prev1, last1);
+            if (fp.ends) ggrow[fp.kq] = (float)(am * out);
         }
     }
     if (ggrow) {  // frames past the last tile: the first one hears the th weights of the last tile's last frame, the others nothing
-        const int klast = min((ntiles * 64 - 1) / h, K - 1);
+        const int klast = last_frame(ntiles, h, K);
         if (lane == 0 && klast + 1 < K) ggrow[klast + 1] = (float)(am * last1);
         for (int kz = klast + 2 + lane; kz < K; kz += 64) ggrow[kz] = 0.f;
     }
-    ga = ds::wave_sum(ga);
-    G.r = ds::wave_sum(G.r);
-    G.i = ds::wave_sum(G.i);
-    if (lane == 0) {
-        if (gamp) gamp[(int64_t)a * m + mm] = (float)ga;
-        gpart[(int64_t)a * m + mm] = make_double2(am * G.r, am * G.i);
-    }
+    store_mode(ga, G, am, lane, am_at, gamp, gpart);
 }
-
-// gd[mm] = -Im sum_a G / sr, gw[mm] = Re sum_a G / sr, the clips added in order
-__global__ void osc_sld_reduce_kernel(const double2* __restrict__ gpart, int A, int m, double inv_sr,
-                                      double* __restrict__ gd, double* __restrict__ gw) {
-    const int mm = blockIdx.x * blockDim.x + threadIdx.x;
-    if (mm >= m) return;
-    double gr = 0.0, gi = 0.0;
-    for (int a = 0; a < A; ++a) {
-        const double2 g = gpart[(int64_t)a * m + mm];
-        gr += g.x;
-        gi += g.y;
-    }
-    gd[mm] = -gi * inv_sr;
-    gw[mm] = gr * inv_sr;
-}
-
-// gforce[a, j] = 0 for S <= j < F: taps that no output sample hears
-__global__ void osc_sld_zero_tail_kernel(float* __restrict__ gforce, int F, int S) {
-    const int j = S + blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < F) gforce[(int64_t)blockIdx.y * F + j] = 0.f;
-}
-
-inline int64_t ntiles_of(int S) { return ds::ceil_div(S, TILE); }
-
-inline bool aligned(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 // The checks both entry points make before those of their own operands' alignment, in their order; `fn` names the entry point
 int check_args(const char* fn, bool pointers, int A, int m, int F, int S, int K, int hop, double sr, const void* work,
                int64_t work_bytes) {
     DS_REQUIRE(pointers, "%s: null pointer", fn);
     DS_REQUIRE(A > 0 && m > 0 && S > 0 && F > 0 && K > 0, "%s: empty problem (A %d, m %d, F %d, S %d, K %d)", fn, A, m, F, S, K);
-    DS_REQUIRE(A <= 65535, "%s: A = %d above 65535", fn, A);
-    DS_REQUIRE(hop > 0 && hop % DS_OSC_SCAN_RUN == 0, "%s: hop = %d is not a positive multiple of %d", fn, hop,
-               DS_OSC_SCAN_RUN);
-    DS_REQUIRE(sr > 0, "%s: sr = %g is not positive", fn, sr);
-    DS_REQUIRE(work_bytes >= ds_osc_slide_workspace_bytes(A, m, S, K, hop), "%s: workspace of %lld bytes, %lld needed", fn,
-               (long long)work_bytes, (long long)ds_osc_slide_workspace_bytes(A, m, S, K, hop));
-    DS_REQUIRE(aligned(work, 16), "%s: work not 16-byte aligned", fn);
-    return DS_OK;
+    if (int rc = osc_bank::check_clips(fn, A)) return rc;
+    if (int rc = osc_bank::check_frames(fn, hop, sr)) return rc;
+    return osc_bank::check_work(fn, work, work_bytes, ds_osc_slide_workspace_bytes(A, m, S, K, hop));
 }
 
 }  // namespace
 
 extern "C" int64_t ds_osc_slide_workspace_bytes(int A, int m, int S, int K, int hop) {
     if (A <= 0 || m <= 0 || S <= 0 || K <= 0 || hop <= 0 || hop % DS_OSC_SCAN_RUN != 0) return 0;
-    return (int64_t)sizeof(double2) * ((int64_t)A * m * ntiles_of(S) + (int64_t)A * m);
+    return osc_bank::workspace_bytes(A, m, S);
 }
 
 extern "C" int ds_osc_slide_fwd(const double* d, const double* w, const float* amp, const float* force, const float* gain,
@@ -308,13 +232,11 @@ extern "C" int ds_osc_slide_fwd(const double* d, const double* w, const float* a
     const int nin = std::min(F, S);
     double2* bnd = static_cast<double2*>(work);
     const double inv_sr = 1.0 / sr;
-    osc_sld_boundary_kernel<false, true><<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(d, w, force, F, nin, gain, K, hop, m, nt,
-                                                                                      inv_sr, bnd);
+    osc_sld_boundary_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(d, w, force, F, nin, gain, K, hop, m, nt, inv_sr, bnd);
     DS_LAUNCH_CHECK("osc_sld_boundary_kernel");
     osc_sld_tile_kernel<false><<<dim3((unsigned)nt, (unsigned)A), 256, 0, st>>>(d, w, amp, force, F, nin, gain, K, hop, m, nt,
                                                                                inv_sr, bnd, y, S, S);
-    DS_LAUNCH_CHECK("osc_sld_tile_kernel");
-    return DS_OK;
+    return DS_LAUNCHED("osc_sld_tile_kernel");
 }
 
 extern "C" int ds_osc_slide_bwd(const float* gy, const double* d, const double* w, const float* amp, const float* force,
@@ -329,26 +251,18 @@ extern "C" int ds_osc_slide_bwd(const float* gy, const double* d, const double* 
                    aligned(gamp, 4) && aligned(gforce, 4) && aligned(ggain, 4),
                "ds_osc_slide_bwd: misaligned operand");
     hipStream_t st = ds::as_stream(stream);
-    const int nt = (int)ntiles_of(S);
-    double2* lbnd = static_cast<double2*>(work);
-    double2* gpart = lbnd + (int64_t)A * m * nt;
     const double inv_sr = 1.0 / sr;
-    osc_sld_boundary_kernel<true, false><<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(d, w, gy, S, S, nullptr, K, hop, m, nt,
-                                                                                      inv_sr, lbnd);
-    DS_LAUNCH_CHECK("osc_sld_boundary_kernel");
-    if (gforce) {
-        osc_sld_tile_kernel<true><<<dim3((unsigned)nt, (unsigned)A), 256, 0, st>>>(d, w, amp, gy, S, S, gain, K, hop, m, nt, inv_sr,
-                                                                                  lbnd, gforce, F, std::min(F, S));
-        DS_LAUNCH_CHECK("osc_sld_tile_kernel");
-        if (F > S) {
-            osc_sld_zero_tail_kernel<<<dim3((unsigned)ds::ceil_div(F - S, 256), (unsigned)A), 256, 0, st>>>(gforce, F, S);
-            DS_LAUNCH_CHECK("osc_sld_zero_tail_kernel");
-        }
-    }
-    osc_sld_mode_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(gy, d, w, amp, force, gain, F, m, S, K, hop, nt, inv_sr,
-                                                                     lbnd, gamp, gpart, ggain);
-    DS_LAUNCH_CHECK("osc_sld_mode_kernel");
-    osc_sld_reduce_kernel<<<(unsigned)ds::ceil_div(m, 64), 64, 0, st>>>(gpart, A, m, inv_sr, gd, gw);
-    DS_LAUNCH_CHECK("osc_sld_reduce_kernel");
-    return DS_OK;
+    return osc_bank::backward(
+        st, A, m, F, S, inv_sr, work, gd, gw, gforce,
+        [&](int nt, double2* lbnd) { return osc_bank::launch_boundary(st, true, d, w, gy, S, S, A, m, nt, inv_sr, lbnd); },
+        [&](int nt, const double2* lbnd) {
+            osc_sld_tile_kernel<true><<<dim3((unsigned)nt, (unsigned)A), 256, 0, st>>>(d, w, amp, gy, S, S, gain, K, hop, m, nt,
+                                                                                      inv_sr, lbnd, gforce, F, std::min(F, S));
+            return DS_LAUNCHED("osc_sld_tile_kernel");
+        },
+        [&](int nt, const double2* lbnd, double2* gpart) {
+            osc_sld_mode_kernel<<<dim3((unsigned)m, (unsigned)A), 64, 0, st>>>(gy, d, w, amp, force, gain, F, m, S, K, hop, nt,
+                                                                             inv_sr, lbnd, gamp, gpart, ggain);
+            return DS_LAUNCHED("osc_sld_mode_kernel");
+        });
 }

@@ -37,6 +37,12 @@ def _restore(ctx, gy):
     return d, w, (amp if ctx.has_amp else None), force, gy.float().contiguous()
 
 
+def _work(query, *dims, device):
+    """The workspace of a recursive bank: ``query`` is its ds_osc_*_workspace_bytes, ``dims`` that query's arguments."""
+    nbytes = query(*dims)
+    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
+
+
 def _grad_buffers(d, w, amp):
     """Uninitialised gradients of d, w and, where there is one, amp: the kernels write every element."""
     return torch.empty_like(d), torch.empty_like(w), (None if amp is None else torch.empty_like(amp))
@@ -103,17 +109,12 @@ class _OscDriven(torch.autograd.Function):
     ds_osc_driven_bwd): any force length, gradients for d, w, amp and force."""
 
     @staticmethod
-    def _work(L, A, m, S, device):
-        nbytes = L.ds_osc_driven_workspace_bytes(A, m, S)
-        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
-
-    @staticmethod
     def forward(ctx, d, w, amp, force, S, sr):
         d, w, amp, force = _prepare(torch.float64, d, w, amp, force)
         A, nF = force.shape
         m = d.shape[0]
         L = _hip.lib()
-        work, nbytes = _OscDriven._work(L, A, m, S, force.device)
+        work, nbytes = _work(L.ds_osc_driven_workspace_bytes, A, m, S, device=force.device)
         y = torch.empty((A, S), dtype=torch.float32, device=force.device)
         p = _hip.ptr
         _hip.check(L.ds_osc_driven_fwd(p(d), p(w), p(amp), p(force), A, m, nF, S, float(sr), p(work), nbytes, p(y),
@@ -127,7 +128,7 @@ class _OscDriven(torch.autograd.Function):
         A, nF = force.shape
         m = d.shape[0]
         L = _hip.lib()
-        work, nbytes = _OscDriven._work(L, A, m, ctx.S, gy.device)
+        work, nbytes = _work(L.ds_osc_driven_workspace_bytes, A, m, ctx.S, device=gy.device)
         gd, gw, gamp = _grad_buffers(d, w, amp)
         gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
         p = _hip.ptr
@@ -142,11 +143,6 @@ class _OscSliding(torch.autograd.Function):
     csrc/osc_slide.hip): a contact that moves while the force acts.  Gradients for d, w, amp, force and gain."""
 
     @staticmethod
-    def _work(L, A, m, S, K, hop, device):
-        nbytes = L.ds_osc_slide_workspace_bytes(A, m, S, K, hop)
-        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
-
-    @staticmethod
     def forward(ctx, d, w, amp, force, gain, hop, S, sr):
         d, w, amp, force = _prepare(torch.float64, d, w, amp, force)
         _hip.require_gpu(gain)
@@ -159,7 +155,7 @@ class _OscSliding(torch.autograd.Function):
         K = gain.shape[1]
         gain_k = gain.detach().float().transpose(1, 2).contiguous()  # the kernels' layout: (A, m, K), frames contiguous
         L = _hip.lib()
-        work, nbytes = _OscSliding._work(L, A, m, S, K, hop, force.device)
+        work, nbytes = _work(L.ds_osc_slide_workspace_bytes, A, m, S, K, hop, device=force.device)
         y = torch.empty((A, S), dtype=torch.float32, device=force.device)
         p = _hip.ptr
         _hip.check(L.ds_osc_slide_fwd(p(d), p(w), p(amp), p(force), p(gain_k), A, m, nF, S, K, hop, float(sr), p(work), nbytes,
@@ -175,7 +171,7 @@ class _OscSliding(torch.autograd.Function):
         A, nF = force.shape
         m, K = d.shape[0], gain_k.shape[2]
         L = _hip.lib()
-        work, nbytes = _OscSliding._work(L, A, m, ctx.S, K, hop, gy.device)
+        work, nbytes = _work(L.ds_osc_slide_workspace_bytes, A, m, ctx.S, K, hop, device=gy.device)
         gd, gw, gamp = _grad_buffers(d, w, amp)
         gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
         ggain = torch.empty_like(gain_k) if ctx.needs_input_grad[4] else None
@@ -212,11 +208,6 @@ class _OscListener(torch.autograd.Function):
     computed only where it is needed."""
 
     @staticmethod
-    def _work(L, A, C, m, S, K, hop, device):
-        nbytes = L.ds_osc_listen_workspace_bytes(A, C, m, S, K, hop)
-        return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
-
-    @staticmethod
     def forward(ctx, d, w, amp, force, hgain, hop, S, sr):
         d, w, amp, force = _prepare(torch.float64, d, w, amp, force)
         _hip.require_gpu(hgain)
@@ -226,7 +217,7 @@ class _OscListener(torch.autograd.Function):
         # the kernels' layout: (A, C, m, K, 2); a gain built as t.conj() carries torch's lazy conjugate bit, which view_as_real refuses
         h = torch.view_as_real(hgain.detach().to(torch.complex64).resolve_conj().contiguous())
         L = _hip.lib()
-        work, nbytes = _OscListener._work(L, A, C, m, S, K, hop, force.device)
+        work, nbytes = _work(L.ds_osc_listen_workspace_bytes, A, C, m, S, K, hop, device=force.device)
         y = torch.empty((A, C, S), dtype=torch.float32, device=force.device)
         p = _hip.ptr
         _hip.check(L.ds_osc_listen_fwd(p(d), p(w), p(amp), p(force), p(h), A, C, m, nF, S, K, hop, float(sr), p(work), nbytes,
@@ -242,7 +233,7 @@ class _OscListener(torch.autograd.Function):
         A, nF = force.shape
         m, C, K = d.shape[0], h.shape[1], h.shape[3]
         L = _hip.lib()
-        work, nbytes = _OscListener._work(L, A, C, m, ctx.S, K, hop, gy.device)
+        work, nbytes = _work(L.ds_osc_listen_workspace_bytes, A, C, m, ctx.S, K, hop, device=gy.device)
         gd, gw, gamp = _grad_buffers(d, w, amp)
         gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
         gh = torch.empty_like(h) if ctx.needs_input_grad[4] else None

@@ -108,5 +108,9 @@ def test_case_list_covers_every_boundary():
     assert {c[4] for c in D.CASES} == set(D.MODE_SETS) and {c[5] for c in D.CASES} == set(D.FORCES)
     assert {c[2] for c in D.CASES} >= {1, 2, 512, 513}
     assert {c[2] - c[3] for c in D.CASES} >= {-1, 0, 7}
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "diffsound_amd", "csrc", "osc_driven.hip")).read()
-    assert f"constexpr int RUN = {Rn};" in src and "constexpr int TILE = 64 * RUN;" in src
+    root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")  # the kernels' constants: osc_scan.h, from the public header
+    src = open(os.path.join(root, "diffsound_amd", "csrc", "osc_scan.h")).read()
+    assert "constexpr int RUN = DS_OSC_SCAN_RUN;" in src and "constexpr int TILE = 64 * RUN;" in src
+    assert f"#define DS_OSC_SCAN_RUN {Rn} " in open(os.path.join(root, "include", "diffsound_hip.h")).read()
+    driven = open(os.path.join(root, "diffsound_amd", "csrc", "osc_driven.hip")).read()
+    assert "constexpr int RUN" not in driven and "constexpr int TILE" not in driven and "using namespace osc_scan;" in driven

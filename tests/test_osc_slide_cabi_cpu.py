@@ -33,8 +33,11 @@ def test_osc_slide_symbols():
     slide, driven, scan = (open(os.path.join(csrc, n)).read() for n in ("osc_slide.hip", "osc_driven.hip", "osc_scan.h"))
     assert '#include "osc_scan.h"' in slide and '#include "osc_scan.h"' in driven
     for helper in ("struct cplx", "cplx cmul(", "cplx zpow(", "double from_prev(", "void load_run(", "cplx run_from_zero(",
-                   "cplx scan_lanes(", "cplx lane_entry(", "cplx tile_exit("):
+                   "cplx scan_lanes(", "cplx lane_entry(", "cplx tile_exit(", "void join_waves(", "double frame_scan(",
+                   "struct frame_pos"):
         assert helper in scan and helper not in driven and helper not in slide, helper
+    sources = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h", ".inc", ".cpp"))]
+    assert [n for n in sources if "bool aligned(" in open(os.path.join(csrc, n)).read()] == ["ds_common.h"]  # ds::aligned
     assert "atomic" not in slide.replace("No atomics", "").replace("no atomics", "")
 
 
