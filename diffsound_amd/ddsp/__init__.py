@@ -1,2 +1,3 @@
 from .biquad import ParametricEQ, biquad_cascade, highpass_biquad, lowpass_biquad  # noqa: F401
+from .reverb import RoomResponse, fir_convolve  # noqa: F401
 from .contact import HertzHammer, contact_force  # noqa: F401

@@ -821,6 +821,40 @@ int ds_biquad_fwd(const float* x, const double* sos, int per_clip, int B, int N,
 int ds_biquad_bwd(const float* gy, const float* x, const double* sos, int per_clip, int B, int N, int S, void* work,
                   int64_t work_bytes, float* gx, double* gsos, ds_stream_t stream);
 
+/* Room response (still ABI 45, three added symbols): a long causal FIR over B rows of N samples - the room of the
+ * receiver's half of a recorded clip (a microphone, a room, a parametric EQ): early reflections and a decaying tail of
+ * thousands of taps, with gradients to the signal and to every tap.  H responses of L taps; B is a multiple of H and row b
+ * uses response b mod H (H = 1: one room for all rows; H = C: one per channel, the channel varying fastest; H = B: one per
+ * row).  Zero initial state, the output cut at N; no sum is approximated and no index is conjugated:
+ *   y[b,t]  = sum_{j=0..min(t, L-1)}      h[b mod H, j] x[b, t-j] ;
+ *   gx[b,s] = sum_{j=0..min(L-1, N-1-s)}  h[b mod H, j] gy[b, s+j] ;
+ *   gh[r,j] = sum_{b = r, r+H, ...} sum_{t=j..N-1} gy[b,t] x[b, t-j], exactly 0 for j >= N (an empty sum).
+ * x, y, gy, gx: (B x N) f32, 4-byte aligned.  h, gh: (H x L) f64, 8-byte aligned.  1 <= H <= B <= DS_FIR_MAX_ROWS,
+ * 1 <= L <= DS_FIR_MAX_TAPS (2 s at 32 kHz; L may exceed N).  Direct form, N L - L^2 / 2 multiply-adds a row, and no FFT: products
+ * and sums are in fp64, y and gx are rounded to fp32 once, on the store, gh stays fp64.  BIT FOR BIT: a response that is a
+ * unit tap at lag k copies x shifted by k bit for bit, with exact zeros in front, as long as the inputs are finite, and the
+ * same holds for gx from gy (a sum of exact zeros and one exact product; a negative zero is the number zero and comes out
+ * as +0).  The three sums are one loop: a lane owns 8 consecutive outputs (y, gx) or lags (gh), keeps a sliding window of
+ * the other operand in registers and reads one broadcast value and one new window value a step from LDS, where both
+ * operands are staged in fp64; a workgroup owns 512 outputs or lags, the heaviest tiles of the causal triangle are launched
+ * first.  The forward needs no workspace.  gh sums N - j samples and B / H rows: the samples are split into chunks of 2048 (a
+ * constant, never a function of the device), the chunks' partial sums go to the workspace and a second launch adds them,
+ * chunks ascending and then rows ascending: ds_fir_workspace_bytes(B, H, N, L) = 8 B ceil(N / 2048) min(L, N) bytes (0 for
+ * arguments that would be refused), 16-byte aligned, needed only where gh is asked for.  No read-modify-write in memory, no
+ * workgroup waits for another: the same inputs give the same bits on any device.  gx and gh may each be NULL: what is NULL
+ * is not computed and does not change the bits of the other.  Asynchronous on the stream, no allocation.
+ * SAFE FOR EVERY x, gy AND h: no index and no trip count depends on the data.  Non-finite inputs yield inf or NaN in the
+ * outputs and nothing else (in the rows and responses they belong to).
+ * Refused (DS_ERR_ARG, message in ds_last_error()), before any device work, in this order: a null required pointer (x, h, y;
+ * gy, x, h, and work where gh is given); B, H, N or L <= 0; B above DS_FIR_MAX_ROWS; L above DS_FIR_MAX_TAPS; H > B or B not a
+ * multiple of H; a misaligned operand; (backward) gx and gh both NULL; a misaligned workspace; work_bytes below the query. */
+#define DS_FIR_MAX_TAPS 65536 /* L */
+#define DS_FIR_MAX_ROWS 65535 /* B: the rows are the launch grid's first axis */
+int64_t ds_fir_workspace_bytes(int B, int H, int N, int L);
+int ds_fir_fwd(const float* x, const double* h, int B, int H, int N, int L, float* y, ds_stream_t stream);
+int ds_fir_bwd(const float* gy, const float* x, const double* h, int B, int H, int N, int L, void* work, int64_t work_bytes,
+               float* gx /*or NULL*/, double* gh /*or NULL*/, ds_stream_t stream);
+
 /* Contact force (still ABI 45, three added symbols): a Hertz hammer - mass[a] > 0, approach speed vel[a], contact stiffness
  * stiff[a] > 0, exponent p >= 1 (1.5 for Hertz) - coupled to the m modes (d [1/s], w [rad/s, damped]: the banks' pair) of the
  * object it strikes through the modal gains gain[a,i] at the contact point (ds_mode_sample_fwd).  The reference has no
