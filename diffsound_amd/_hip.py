@@ -279,6 +279,31 @@ def check(status, what):
         raise RuntimeError(f"{what} failed (status {status}): {msg.decode() if msg else ''}")
 
 
+def call(name, *args):
+    """The entry point ``name`` with ``args`` as they stand (one that takes no stream); RuntimeError on a non-zero status."""
+    check(getattr(lib(), name)(*args), name)
+
+
+def launch(name, *args, device=None):
+    """The entry point ``name`` with ``args`` and, last, the current stream.  ``device``: the launch runs with that device
+    current and on its stream - every caller outside the operator layer passes its operands' device.  None: the calling
+    thread's device as it is (the operator layer: its lane thread has set the device, and a guard per launch would cost
+    what ``stream_ptr`` saves)."""
+    if device is not None:
+        with torch.cuda.device(device):  # (the stream below is then that device's)
+            return launch(name, *args)
+    status = getattr(lib(), name)(*args, stream_ptr())
+    if status != 0:  # (tested here: the operator layer's success path does without one more Python call)
+        check(status, name)
+
+
+def workspace(name, *dims, device, dtype=torch.uint8):
+    """(uninitialised tensor, count) for the query ``name`` (a ds_*_workspace_{bytes,floats,doubles}) of ``dims``: ``count``
+    elements of ``dtype`` on ``device``."""
+    count = getattr(lib(), name)(*dims)
+    return torch.empty(count, dtype=dtype, device=device), count
+
+
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
@@ -418,8 +443,8 @@ def host_start_block(G, ny, b, ortho_tol, eps):
     cx = torch.empty((b, b), dtype=torch.float64)
     amp, route = _D(0.0), _I(0)
     with blas_one_thread():
-        check(lib().ds_host_start_block(ctypes.byref(lapack_table()), G.data_ptr(), ny, b, float(ortho_tol), float(eps), lam.data_ptr(),
-                                        coef.data_ptr(), cx.data_ptr(), ctypes.byref(amp), ctypes.byref(route)), "ds_host_start_block")
+        call("ds_host_start_block", ctypes.byref(lapack_table()), G.data_ptr(), ny, b, float(ortho_tol), float(eps), lam.data_ptr(),
+             coef.data_ptr(), cx.data_ptr(), ctypes.byref(amp), ctypes.byref(route))
     return None if route.value else (lam, coef, cx, amp.value)
 
 
@@ -434,8 +459,8 @@ def host_polish(GK, coefs, GM, k):
     C = torch.empty((b, b), dtype=torch.float64)
     qs = torch.empty((len(GK) + 1, k), dtype=torch.float64)
     with blas_one_thread():
-        check(lib().ds_host_polish(ctypes.byref(lapack_table()), len(GK), gk.data_ptr(), cf.data_ptr(), GM.data_ptr(), b, k, E.data_ptr(),
-                                   C.data_ptr(), qs.data_ptr()), "ds_host_polish")
+        call("ds_host_polish", ctypes.byref(lapack_table()), len(GK), gk.data_ptr(), cf.data_ptr(), GM.data_ptr(), b, k, E.data_ptr(),
+             C.data_ptr(), qs.data_ptr())
     return E, C, qs
 
 
@@ -447,8 +472,8 @@ def host_raw_basis(GG, Gxp, lam_locked, ny, ncl, nxp, na, ortho_tol, eps):
     Qw = torch.empty((ny + ncl + nxp + na, na), dtype=torch.float64)
     route = _I(0)
     with blas_one_thread():
-        check(lib().ds_host_raw_basis(ctypes.byref(lapack_table()), GG.data_ptr(), Gxp.data_ptr(), lam_locked.data_ptr(), ny, ncl, nxp, na,
-                                      float(ortho_tol), float(eps), G.data_ptr(), Qw.data_ptr(), ctypes.byref(route)), "ds_host_raw_basis")
+        call("ds_host_raw_basis", ctypes.byref(lapack_table()), GG.data_ptr(), Gxp.data_ptr(), lam_locked.data_ptr(), ny, ncl, nxp, na,
+             float(ortho_tol), float(eps), G.data_ptr(), Qw.data_ptr(), ctypes.byref(route))
     return None if route.value else (G, Qw)
 
 
@@ -459,8 +484,7 @@ def host_rr_step(G, na):
     E = torch.empty(na, dtype=torch.float64)
     Z1, Zp = torch.empty((sz, na), dtype=torch.float64), torch.empty((sz, na), dtype=torch.float64)
     with blas_one_thread():
-        check(lib().ds_host_rr_step(ctypes.byref(lapack_table()), G.data_ptr(), sz, na, E.data_ptr(), Z1.data_ptr(), Zp.data_ptr()),
-              "ds_host_rr_step")
+        call("ds_host_rr_step", ctypes.byref(lapack_table()), G.data_ptr(), sz, na, E.data_ptr(), Z1.data_ptr(), Zp.data_ptr())
     return E, Z1, Zp
 
 
@@ -472,20 +496,17 @@ class Pattern:
         if t.device.type != "cpu" or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 2:
             raise ValueError("Pattern: tets must be a contiguous (T, N) int32 CPU tensor")
         handle = ctypes.c_void_p()
-        check(lib().ds_pattern_build(ptr(t), t.shape[0], t.shape[1], nv, nthreads, ctypes.byref(handle)),
-              "ds_pattern_build")
+        call("ds_pattern_build", ptr(t), t.shape[0], t.shape[1], nv, nthreads, ctypes.byref(handle))
         try:
             a, b, c = _I64(), _I64(), _I64()
-            check(lib().ds_pattern_sizes(handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
-                  "ds_pattern_sizes")
+            call("ds_pattern_sizes", handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
             self.nv, self.nnzb, self.ncontrib = a.value, b.value, c.value
             self.rowptr = torch.empty(self.nv + 1, dtype=torch.int32)
             self.colidx = torch.empty(self.nnzb, dtype=torch.int32)
             self.diagidx = torch.empty(self.nv, dtype=torch.int32)
             self.cptr = torch.empty(self.nnzb + 1, dtype=torch.int32)
             self.clist = torch.empty(self.ncontrib, dtype=torch.int32)
-            check(lib().ds_pattern_export(handle, ptr(self.rowptr), ptr(self.colidx), ptr(self.diagidx),
-                                          ptr(self.cptr), ptr(self.clist)), "ds_pattern_export")
+            call("ds_pattern_export", handle, ptr(self.rowptr), ptr(self.colidx), ptr(self.diagidx), ptr(self.cptr), ptr(self.clist))
         finally:
             lib().ds_pattern_free(handle)
 
@@ -499,12 +520,10 @@ class DevicePattern:
         if not t.is_cuda or t.dtype != torch.int32 or not t.is_contiguous() or t.dim() != 2:
             raise ValueError("DevicePattern: tets must be a contiguous (T, N) int32 HIP tensor")
         handle = ctypes.c_void_p()
-        check(lib().ds_dpattern_build(ptr(t), t.shape[0], t.shape[1], nv, cap, stream_ptr(), ctypes.byref(handle)),
-              "ds_dpattern_build")
+        call("ds_dpattern_build", ptr(t), t.shape[0], t.shape[1], nv, cap, stream_ptr(), ctypes.byref(handle))  # (stream not last)
         try:
             a, b, c, d, e = _I64(), _I64(), _I64(), _I64(), _I64()
-            check(lib().ds_dpattern_sizes(handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d),
-                                          ctypes.byref(e)), "ds_dpattern_sizes")
+            call("ds_dpattern_sizes", handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c), ctypes.byref(d), ctypes.byref(e))
             self.nv, self.nnzb, self.ncontrib, self.ne, self.ngroups, self.nchunks = nv, a.value, b.value, c.value, d.value, e.value
             self.single = self.nchunks == self.ngroups  # every group is one chunk
             mk = lambda n: torch.empty(n, dtype=torch.int32, device=t.device)
@@ -513,9 +532,8 @@ class DevicePattern:
             self.gptr, self.gent, self.goff, self.kperm = mk(self.ngroups + 1), mk(self.ne), mk(self.ne + 1), mk(self.nnzb)
             self.utab = torch.empty((self.ngroups, 2), dtype=torch.int32, device=t.device)
             self.ctab = torch.empty((self.nchunks, 4), dtype=torch.int32, device=t.device)
-            check(lib().ds_dpattern_export(handle, ptr(self.rowptr), ptr(self.colidx), ptr(self.diagidx), ptr(self.cptr),
-                                           ptr(self.clist), ptr(self.gptr), ptr(self.gent), ptr(self.goff),
-                                           ptr(self.kperm), ptr(self.utab), ptr(self.ctab), stream_ptr()), "ds_dpattern_export")
+            launch("ds_dpattern_export", handle, ptr(self.rowptr), ptr(self.colidx), ptr(self.diagidx), ptr(self.cptr),
+                   ptr(self.clist), ptr(self.gptr), ptr(self.gent), ptr(self.goff), ptr(self.kperm), ptr(self.utab), ptr(self.ctab))
             torch.cuda.current_stream(t.device).synchronize()  # the handle's arrays are freed below
         finally:
             lib().ds_dpattern_free(handle)
@@ -533,8 +551,7 @@ def edge_table(tets4, nv):
     eb = torch.empty(6 * T, dtype=torch.int64, device=t.device)
     te = torch.empty((T, 6), dtype=torch.int64, device=t.device)
     ne = _I64()
-    with torch.cuda.device(t.device):
-        check(lib().ds_edge_table(ptr(t), T, nv, ptr(ea), ptr(eb), ptr(te), ctypes.byref(ne), stream_ptr()), "ds_edge_table")
+    launch("ds_edge_table", ptr(t), T, nv, ptr(ea), ptr(eb), ptr(te), ctypes.byref(ne), device=t.device)
     return ea[:ne.value], eb[:ne.value], te
 
 
@@ -549,8 +566,7 @@ def unique_rows3(xyz):
     inv = torch.empty(n, dtype=torch.int64, device=x.device)
     first = torch.empty(n, dtype=torch.int64, device=x.device)
     nu = _I64()
-    with torch.cuda.device(x.device):
-        check(lib().ds_unique_rows3(ptr(x), n, ptr(inv), ptr(first), ctypes.byref(nu), stream_ptr()), "ds_unique_rows3")
+    launch("ds_unique_rows3", ptr(x), n, ptr(inv), ptr(first), ctypes.byref(nu), device=x.device)
     return inv, first[:nu.value]
 
 
@@ -559,17 +575,16 @@ class Groups:
 
     def __init__(self, rowptr_cpu, colidx_cpu, nv):
         handle = ctypes.c_void_p()
-        check(lib().ds_groups_build(ptr(rowptr_cpu), ptr(colidx_cpu), nv, ctypes.byref(handle)), "ds_groups_build")
+        call("ds_groups_build", ptr(rowptr_cpu), ptr(colidx_cpu), nv, ctypes.byref(handle))
         try:
             a, b = _I64(), _I64()
-            check(lib().ds_groups_sizes(handle, ctypes.byref(a), ctypes.byref(b)), "ds_groups_sizes")
+            call("ds_groups_sizes", handle, ctypes.byref(a), ctypes.byref(b))
             self.ngroups, self.ne = a.value, b.value
             self.gptr = torch.empty(self.ngroups + 1, dtype=torch.int32)
             self.gent = torch.empty(self.ne, dtype=torch.int32)
             self.goff = torch.empty(self.ne + 1, dtype=torch.int32)
             self.kperm = torch.empty(colidx_cpu.numel(), dtype=torch.int32)
-            check(lib().ds_groups_export(handle, ptr(self.gptr), ptr(self.gent), ptr(self.goff), ptr(self.kperm)),
-                  "ds_groups_export")
+            call("ds_groups_export", handle, ptr(self.gptr), ptr(self.gent), ptr(self.goff), ptr(self.kperm))
         finally:
             lib().ds_groups_free(handle)
 

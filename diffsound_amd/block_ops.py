@@ -82,7 +82,7 @@ class _HipBlockOps:
         self.nv = nv
         self.n = 3 * nv
         self.device = device
-        self._L = _hip.lib()
+        _hip.lib()  # (a missing or stale library is reported when the operator is built, not at its first launch)
         self._gram_ws = None
         self._native_ws = {}
         self.gram_exact = False
@@ -91,20 +91,20 @@ class _HipBlockOps:
         self.counts = dict(apply_K_cols=0, apply_M_cols=0, gram=0, mix=0, mix64=0)
 
     # ------------------------------------------------------------------ sparse products
-    def _spmm_chunks(self, kind, vals, vt, X, out, maxc, what):
+    def _spmm_chunks(self, kind, vals, vt, X, out, maxc):
         """out <- A X through ds_spmm_bsr3, ``maxc`` columns per launch."""
         p = _hip.ptr
         for c0 in range(0, X.shape[1], maxc):
             c1 = min(X.shape[1], c0 + maxc)
             xs, os_ = X[:, c0:c1], out[:, c0:c1]
-            _hip.check(self._L.ds_spmm_bsr3(kind, p(self.rowptr), p(self.colidx), p(vals), p(vt), self.nv, p(xs),
-                                            _ld(xs), p(os_), _ld(os_), c1 - c0, _hip.stream_ptr()), what)
+            _hip.launch("ds_spmm_bsr3", kind, p(self.rowptr), p(self.colidx), p(vals), p(vt), self.nv, p(xs), _ld(xs), p(os_), _ld(os_),
+                        c1 - c0)
 
     def _spmm(self, kind, vals, X, out):
         if out.shape != X.shape:
             raise ValueError("spmm: shape mismatch")
         vt = self.k32t if (kind == 0 and vals is self.k32) else None
-        self._spmm_chunks(kind, vals, vt, X, out, 256 if kind < 2 else 128, "ds_spmm_bsr3")
+        self._spmm_chunks(kind, vals, vt, X, out, 256 if kind < 2 else 128)
 
     @staticmethod
     def col_slices(c):
@@ -185,9 +185,9 @@ class _HipBlockOps:
         pp = _hip.ptr
         m4 = self._mfma32
         vals = self.m4 if epilogue == 3 else self.k4
-        _hip.check(self._L.ds_spmm_union32m(epilogue, self._level_tag, *_mfma_ptrs(m4, _MFMA_KEYS32), pp(vals), vals.numel() * 4,
-                                            self.colidx.shape[0], m4["ngroups"], m4["max_entries"], m4["max_batch_blocks"], self.nv,
-                                            pp(X), _ld(X), pp(Y), _ld(Y), X.shape[1], _hip.stream_ptr()), "ds_spmm_union32m")
+        _hip.launch("ds_spmm_union32m", epilogue, self._level_tag, *_mfma_ptrs(m4, _MFMA_KEYS32), pp(vals), vals.numel() * 4,
+                    self.colidx.shape[0], m4["ngroups"], m4["max_entries"], m4["max_batch_blocks"], self.nv, pp(X), _ld(X), pp(Y),
+                    _ld(Y), X.shape[1])
 
     def twolevel_apply(self, smooth, coarse, R, W, D, AD, Rr, Rc, Ec, Dc, ADc, Wc, R16=None, prepared=False):
         """The whole two-level V-cycle W = B R through the native driver (ds_twolevel_apply): one call instead of
@@ -220,7 +220,7 @@ class _HipBlockOps:
         _wire_cycle_scratch(d, D, AD, Rr, Wc, Rc, Ec, Dc, ADc, R16)
         if prepared:
             d.storage |= _hip.TL_PREPARED
-        _hip.check(self._L.ds_twolevel_apply(ctypes.byref(d), _hip.stream_ptr()), "ds_twolevel_apply")
+        _hip.launch("ds_twolevel_apply", ctypes.byref(d))
         c = R.shape[1]
         self.counts["apply_K_cols"] += c * (max(smooth[0] - 1, 0) + 1 + smooth[0])
         co.counts["apply_K_cols"] += c * (coarse[0] - 1)
@@ -242,8 +242,8 @@ class _HipBlockOps:
             return False
         b = R.shape[1]
         scr = self._scratch("native_cheb", (3, self.n, b), torch.bfloat16)
-        _hip.check(self._L.ds_chebyshev_apply16(ctypes.byref(d), R.data_ptr(), _ld(R), W.data_ptr(), _ld(W), scr[0].data_ptr(),
-                                                scr[1].data_ptr(), scr[2].data_ptr(), b, b, _hip.stream_ptr()), "ds_chebyshev_apply16")
+        _hip.launch("ds_chebyshev_apply16", ctypes.byref(d), R.data_ptr(), _ld(R), W.data_ptr(), _ld(W), scr[0].data_ptr(),
+                    scr[1].data_ptr(), scr[2].data_ptr(), b, b)
         self.counts["apply_K_cols"] += b * (precond.degree - 1)
         return True
 
@@ -303,7 +303,7 @@ class _HipBlockOps:
         need = self._native_ws.get(key)
         if need is None:  # the split count depends on the shape: take the largest need over every shape the driver forms
             # (q: the active width na, 2 na for [K W | M W] of the Ritz step on the raw basis, p itself for the full refresh)
-            need = max(self._L.ds_gram_workspace_bytes(self.n, p_, q_)
+            need = max(_hip.lib().ds_gram_workspace_bytes(self.n, p_, q_)
                        for p_ in range(4, m + 1, 4) for q_ in sorted(set(range(4, 2 * b + 1, 4)) | {p_}) if q_ <= 3 * b)
             self._native_ws[key] = need
         self._gram_workspace(need)
@@ -348,8 +348,7 @@ class _HipBlockOps:
         hist_h = (ctypes.c_double * (cfg.maxit + 1))()
         d.lam, d.rerr, d.history, d.history_cap = lam_h, rerr_h, hist_h, cfg.maxit + 1
         with _hip.blas_one_thread():
-            _hip.check(self._L.ds_lobpcg_iterate(ctypes.byref(d), ctypes.byref(_hip.lapack_table()), _hip.stream_ptr()),
-                       "ds_lobpcg_iterate")
+            _hip.launch("ds_lobpcg_iterate", ctypes.byref(d), ctypes.byref(_hip.lapack_table()))
         it = int(d.iterations)
         lam_t = torch.tensor(list(lam_h), dtype=torch.float64, device=self.device)
         rel_t = torch.tensor(list(rerr_h), dtype=torch.float64, device=self.device)
@@ -360,20 +359,17 @@ class _HipBlockOps:
     def _union(self, epilogue, X, Y, R0=None, c1=0.0, c2=0.0, first=False, Wprev=None):
         pp = _hip.ptr
         vals = self.mgrp if epilogue == 3 else self.kgrp
-        _hip.check(self._L.ds_spmm_union(epilogue, self._level_tag, *self._union_tabs(), pp(vals),
-                                         vals.shape[0], self.nv, pp(X), _ld(X), pp(Y), _ld(Y), pp(R0),
-                                         0 if R0 is None else _ld(R0), pp(self.dinv) if epilogue == 1 else None,
-                                         X.shape[1], float(c1), float(c2), int(bool(first)), pp(Wprev),
-                                         0 if Wprev is None else _ld(Wprev), _hip.stream_ptr()),
-                   "ds_spmm_union")
+        _hip.launch("ds_spmm_union", epilogue, self._level_tag, *self._union_tabs(), pp(vals), vals.shape[0], self.nv, pp(X), _ld(X),
+                    pp(Y), _ld(Y), pp(R0), 0 if R0 is None else _ld(R0), pp(self.dinv) if epilogue == 1 else None, X.shape[1],
+                    float(c1), float(c2), int(bool(first)), pp(Wprev), 0 if Wprev is None else _ld(Wprev))
 
     def _narrow(self, kind, X, Y):
         """<= 16 columns: the kernel that deals a wave's lanes over the union's entries (ds_spmm_union_narrow)."""
         pp = _hip.ptr
         utab, ctab, ngroups, _, gent = self._union_tabs()
         vals = self.mgrp if kind == 3 else self.kgrp
-        _hip.check(self._L.ds_spmm_union_narrow(kind, self._level_tag, utab, ctab, ngroups, gent, pp(vals), vals.shape[0], self.nv,
-                                                pp(X), _ld(X), pp(Y), _ld(Y), X.shape[1], _hip.stream_ptr()), "ds_spmm_union_narrow")
+        _hip.launch("ds_spmm_union_narrow", kind, self._level_tag, utab, ctab, ngroups, gent, pp(vals), vals.shape[0], self.nv,
+                    pp(X), _ld(X), pp(Y), _ld(Y), X.shape[1])
 
     def apply_K(self, X, out):
         if self._union32_ok(X, out):
@@ -403,9 +399,8 @@ class _HipBlockOps:
         tabs = self._union_tabs()
         for c0, c1 in self.col_slices(X.shape[1]):
             xs, ks, ms = X[:, c0:c1], KX[:, c0:c1], MX[:, c0:c1]
-            _hip.check(self._L.ds_spmm_union_km(self._level_tag, *tabs, pp(self.kgrp), pp(self.mgrp), self.kgrp.shape[0], self.nv,
-                                                pp(xs), _ld(xs), pp(ks), _ld(ks), pp(ms), _ld(ms), c1 - c0, _hip.stream_ptr()),
-                       "ds_spmm_union_km")
+            _hip.launch("ds_spmm_union_km", self._level_tag, *tabs, pp(self.kgrp), pp(self.mgrp), self.kgrp.shape[0], self.nv,
+                        pp(xs), _ld(xs), pp(ks), _ld(ks), pp(ms), _ld(ms), c1 - c0)
         self.counts["apply_K_cols"] += X.shape[1]
         self.counts["apply_M_cols"] += X.shape[1]
 
@@ -433,14 +428,13 @@ class _HipBlockOps:
         benchmark's row count, ~1e-7 on a few hundred rows); ops with gram_exact set always take the fp64 MFMA."""
         exact = exact or self.gram_exact
         p, q = A.shape[1], B.shape[1]
-        need = self._L.ds_gram_workspace_bytes(self.n, p, q)
-        self._gram_workspace(need)
+        self._gram_workspace(_hip.lib().ds_gram_workspace_bytes(self.n, p, q))
         G = torch.empty((p, q), dtype=torch.float64, device=self.device)
         adt = DS_F64 if A.dtype == torch.float64 else DS_F32
         bdt = DS_F64 if B.dtype == torch.float64 else DS_F32
         pp = _hip.ptr
-        _hip.check(self._L.ds_gram(pp(A), adt, _ld(A), p, pp(B), bdt, _ld(B), q, self.n, int(bool(symmetric)) | (2 if exact else 0), pp(G),
-                                   pp(self._gram_ws), self._gram_ws.numel(), _hip.stream_ptr()), "ds_gram")
+        _hip.launch("ds_gram", pp(A), adt, _ld(A), p, pp(B), bdt, _ld(B), q, self.n, int(bool(symmetric)) | (2 if exact else 0), pp(G),
+                    pp(self._gram_ws), self._gram_ws.numel())
         self.counts["gram"] += 1
         return G
 
@@ -457,12 +451,10 @@ class _HipBlockOps:
                 off += blk.shape[1]
             return arr, off
         (ta, p), (tb, q) = table(A_blocks), table(B_blocks)
-        need = self._L.ds_gram_workspace_bytes(self.n, p, q)
-        self._gram_workspace(need)
+        self._gram_workspace(_hip.lib().ds_gram_workspace_bytes(self.n, p, q))
         G = torch.empty((p, q), dtype=torch.float64, device=self.device)
-        _hip.check(self._L.ds_gram64_blocks(len(A_blocks), ctypes.addressof(ta), len(B_blocks), ctypes.addressof(tb), self.n,
-                                            int(bool(symmetric)), _hip.ptr(G), _hip.ptr(self._gram_ws), self._gram_ws.numel(),
-                                            _hip.stream_ptr()), "ds_gram64_blocks")
+        _hip.launch("ds_gram64_blocks", len(A_blocks), ctypes.addressof(ta), len(B_blocks), ctypes.addressof(tb), self.n,
+                    int(bool(symmetric)), _hip.ptr(G), _hip.ptr(self._gram_ws), self._gram_ws.numel())
         self.counts["gram"] += 1
         return G
 
@@ -479,8 +471,7 @@ class _HipBlockOps:
             raise ValueError("mix: shape mismatch")
         C32 = C.to(torch.float32).contiguous()
         pp = _hip.ptr
-        _hip.check(self._L.ds_mix(pp(A), _ld(A), p, pp(C32), q, pp(out), _ld(out), self.n, float(alpha),
-                                  float(beta), _hip.stream_ptr()), "ds_mix")
+        _hip.launch("ds_mix", pp(A), _ld(A), p, pp(C32), q, pp(out), _ld(out), self.n, float(alpha), float(beta))
         self.counts["mix"] += 1
 
     def mix64(self, blocks, C, out=None, alpha=1.0, beta=0.0):
@@ -516,8 +507,8 @@ class _HipBlockOps:
             arr = (_hip.Block64 * len(part))()
             for d, (blk, r) in zip(arr, part):
                 d.a, d.lda, d.p, d.offset = pp(blk), _ld(blk), blk.shape[1], r
-            _hip.check(self._L.ds_mix64(len(part), ctypes.addressof(arr), pp(C), _ld(C), q, pp(out), _ld(out), self.n,
-                                        float(alpha), float(beta if i0 == 0 else 1.0), _hip.stream_ptr()), "ds_mix64")
+            _hip.launch("ds_mix64", len(part), ctypes.addressof(arr), pp(C), _ld(C), q, pp(out), _ld(out), self.n, float(alpha),
+                        float(beta if i0 == 0 else 1.0))
         self.counts["mix64"] += 1
         return out
 
@@ -530,12 +521,12 @@ class _HipBlockOps:
             R = torch.addcmul(KX, MX, lam[None, :], value=-1.0)
             return (R * R).sum(0), (X * X).sum(0)
         pp = _hip.ptr
-        need = self._L.ds_residual64_workspace_doubles(b)
+        need = _hip.lib().ds_residual64_workspace_doubles(b)
         ws = self._scratch("residual64_ws", (need,), torch.float64)
         out = torch.empty((2, b), dtype=torch.float64, device=self.device)
         lam = lam.to(torch.float64).contiguous()
-        _hip.check(self._L.ds_residual64_norms(pp(KX), _ld(KX), pp(MX), _ld(MX), pp(X), _ld(X), pp(lam), self.n, b, pp(ws), need,
-                                               pp(out[0]), pp(out[1]), _hip.stream_ptr()), "ds_residual64_norms")
+        _hip.launch("ds_residual64_norms", pp(KX), _ld(KX), pp(MX), _ld(MX), pp(X), _ld(X), pp(lam), self.n, b, pp(ws), need,
+                    pp(out[0]), pp(out[1]))
         return out[0], out[1]
 
     def residual64_scaled(self, KX, MX, lam, scale, idx, out=None):
@@ -550,8 +541,7 @@ class _HipBlockOps:
             raise ValueError("residual64_scaled: out is (n x len(idx)) fp32 with unit column stride")
         cols = idx.to(torch.int32).contiguous()
         lam, scale = lam.to(torch.float64).contiguous(), scale.to(torch.float64).contiguous()
-        _hip.check(self._L.ds_residual64_scaled(pp(KX), _ld(KX), pp(MX), _ld(MX), pp(lam), pp(scale), pp(cols), nact, pp(R), _ld(R),
-                                                self.n, _hip.stream_ptr()), "ds_residual64_scaled")
+        _hip.launch("ds_residual64_scaled", pp(KX), _ld(KX), pp(MX), _ld(MX), pp(lam), pp(scale), pp(cols), nact, pp(R), _ld(R), self.n)
         return R
 
     def mix_inplace(self, W, T):
@@ -565,7 +555,7 @@ class _HipBlockOps:
     # ------------------------------------------------------------------ fused elementwise
     def _residual_ws(self, ncols):
         u = self.sys.groups["union"]
-        need = self._L.ds_union_residual_workspace_bytes(u["ngroups"], ncols)
+        need = _hip.lib().ds_union_residual_workspace_bytes(u["ngroups"], ncols)
         ws = self._tmp.get("residual_ws")
         if ws is None or ws.numel() < need:
             ws = self._tmp["residual_ws"] = torch.empty((need,), dtype=torch.uint8, device=self.device)
@@ -591,9 +581,9 @@ class _HipBlockOps:
         ws = self._residual_ws(max(c1 - c0 for c0, c1 in slices))
         for c0, c1 in slices:
             xs, rs = X[:, c0:c1], R[:, c0:c1]
-            _hip.check(self._L.ds_union_residual(self._level_tag, *tabs, pp(self.kgrp), pp(self.mgrp), self.kgrp.shape[0], self.nv,
-                                                 pp(xs), _ld(xs), pp(lam64[c0:]), pp(rs), _ld(rs), c1 - c0, pp(ws), ws.numel(),
-                                                 pp(self._nrm[0, c0:]), pp(self._nrm[1, c0:]), _hip.stream_ptr()), "ds_union_residual")
+            _hip.launch("ds_union_residual", self._level_tag, *tabs, pp(self.kgrp), pp(self.mgrp), self.kgrp.shape[0], self.nv,
+                        pp(xs), _ld(xs), pp(lam64[c0:]), pp(rs), _ld(rs), c1 - c0, pp(ws), ws.numel(), pp(self._nrm[0, c0:]),
+                        pp(self._nrm[1, c0:]))
         self.counts["apply_K_cols"] += b
         self.counts["apply_M_cols"] += b
         return self._norms(b)
@@ -606,10 +596,9 @@ class _HipBlockOps:
         lam64 = lam.to(torch.float64).contiguous()
         pp = _hip.ptr
         ws = self._residual_ws(b)
-        _hip.check(self._L.ds_union_residual_pre(self._level_tag, *self._union_tabs(), pp(self.kgrp), pp(self.mgrp), self.kgrp.shape[0],
-                                                 self.nv, pp(X), _ld(X), pp(lam64), pp(self.dinv), float(c), pp(R16), _ld(R16), pp(W1),
-                                                 _ld(W1), b, pp(ws), ws.numel(), pp(self._nrm[0]), pp(self._nrm[1]), _hip.stream_ptr()),
-                   "ds_union_residual_pre")
+        _hip.launch("ds_union_residual_pre", self._level_tag, *self._union_tabs(), pp(self.kgrp), pp(self.mgrp), self.kgrp.shape[0],
+                    self.nv, pp(X), _ld(X), pp(lam64), pp(self.dinv), float(c), pp(R16), _ld(R16), pp(W1), _ld(W1), b, pp(ws),
+                    ws.numel(), pp(self._nrm[0]), pp(self._nrm[1]))
         self.counts["apply_K_cols"] += b
         self.counts["apply_M_cols"] += b
         return self._norms(b)
@@ -620,19 +609,18 @@ class _HipBlockOps:
         lam64 = lam.to(torch.float64).contiguous()
         pp = _hip.ptr
         src = R if src is None else src
-        _hip.check(self._L.ds_residual(pp(src), _ld(src), pp(R), _ld(R), pp(MX), _ld(MX), pp(X), _ld(X), pp(lam64), self.n, b,
-                                       pp(self._nrm[0]), pp(self._nrm[1]), _hip.stream_ptr()), "ds_residual")
+        _hip.launch("ds_residual", pp(src), _ld(src), pp(R), _ld(R), pp(MX), _ld(MX), pp(X), _ld(X), pp(lam64), self.n, b,
+                    pp(self._nrm[0]), pp(self._nrm[1]))
         return self._norms(b)
 
     def cheb_init(self, R, D, W, c):
         pp = _hip.ptr
-        _hip.check(self._L.ds_cheb_init(pp(R), _ld(R), pp(D), _ld(D), pp(W), _ld(W), pp(self.dinv), self.nv,
-                                        R.shape[1], float(c), _hip.stream_ptr()), "ds_cheb_init")
+        _hip.launch("ds_cheb_init", pp(R), _ld(R), pp(D), _ld(D), pp(W), _ld(W), pp(self.dinv), self.nv, R.shape[1], float(c))
 
     def cheb_step(self, AD, R, D, W, c1, c2):
         pp = _hip.ptr
-        _hip.check(self._L.ds_cheb_step(pp(AD), _ld(AD), pp(R), _ld(R), pp(D), _ld(D), pp(W), _ld(W), pp(self.dinv),
-                                        self.nv, R.shape[1], float(c1), float(c2), _hip.stream_ptr()), "ds_cheb_step")
+        _hip.launch("ds_cheb_step", pp(AD), _ld(AD), pp(R), _ld(R), pp(D), _ld(D), pp(W), _ld(W), pp(self.dinv), self.nv, R.shape[1],
+                    float(c1), float(c2))
 
     def cheb_spmm(self, Wk, Wprev, R0, c1, c2, first):
         """Wprev <- Wk + c1 (Wk - Wprev) + c2 T (R0 - K Wk): one fused launch per polynomial term."""
@@ -640,9 +628,8 @@ class _HipBlockOps:
             self._union(1, Wk, Wprev, R0, c1, c2, first)
         else:
             pp = _hip.ptr
-            _hip.check(self._L.ds_cheb_spmm(pp(self.rowptr), pp(self.colidx), pp(self.k32), self.nv, pp(Wk), _ld(Wk),
-                                            pp(Wprev), _ld(Wprev), pp(R0), _ld(R0), pp(self.dinv), Wk.shape[1],
-                                            float(c1), float(c2), int(bool(first)), _hip.stream_ptr()), "ds_cheb_spmm")
+            _hip.launch("ds_cheb_spmm", pp(self.rowptr), pp(self.colidx), pp(self.k32), self.nv, pp(Wk), _ld(Wk), pp(Wprev), _ld(Wprev),
+                        pp(R0), _ld(R0), pp(self.dinv), Wk.shape[1], float(c1), float(c2), int(bool(first)))
         self.counts["apply_K_cols"] += Wk.shape[1]
 
     _cheb_spmm_launch = cheb_spmm  # (the name the benchmark's roofline and tools/mb_*.py time the launch under)
@@ -666,12 +653,12 @@ class _HipBlockOps:
         pp = _hip.ptr
         mt = self._mfma
         tail = (self.nv, pp(Wk), _ld(Wk), pp(Wprev), _ld(Wprev), 0, pp(R0), _ld(R0), pp(self.dinv), Wk.shape[1], float(c1), float(c2),
-                int(bool(first)), None, 0, _hip.stream_ptr())
+                int(bool(first)), None, 0)
         if mt is not None and self.kc is not None:
-            _hip.check(self._L.ds_spmm_union16m(1, mt["G"], self._level_tag, *_mfma_ptrs(mt), pp(self.kc), self.kc.shape[0], mt["ngroups"],
-                                                mt["max_entries"], mt["max_batch_blocks"], *tail), "ds_spmm_union16m")
+            _hip.launch("ds_spmm_union16m", 1, mt["G"], self._level_tag, *_mfma_ptrs(mt), pp(self.kc), self.kc.shape[0], mt["ngroups"],
+                        mt["max_entries"], mt["max_batch_blocks"], *tail)
         else:
-            _hip.check(self._L.ds_spmm_union16(1, *self._union_tabs(), pp(self.kgrp), self.kgrp.shape[0], *tail), "ds_spmm_union16")
+            _hip.launch("ds_spmm_union16", 1, *self._union_tabs(), pp(self.kgrp), self.kgrp.shape[0], *tail)
 
     # ------------------------------------------------------------------ two-level preconditioner pieces
     def spmm_residual(self, X, R0, Y):
@@ -680,15 +667,13 @@ class _HipBlockOps:
             self._union(2, X, Y, R0)
         else:
             pp = _hip.ptr
-            _hip.check(self._L.ds_spmm_residual(pp(self.rowptr), pp(self.colidx), pp(self.k32), self.nv, pp(X), _ld(X),
-                                                pp(R0), _ld(R0), pp(Y), _ld(Y), X.shape[1], _hip.stream_ptr()),
-                       "ds_spmm_residual")
+            _hip.launch("ds_spmm_residual", pp(self.rowptr), pp(self.colidx), pp(self.k32), self.nv, pp(X), _ld(X), pp(R0), _ld(R0),
+                        pp(Y), _ld(Y), X.shape[1])
         self.counts["apply_K_cols"] += X.shape[1]
 
     def _transfer(self, ptr_, col, w, nrows, X, Y, beta):
         pp = _hip.ptr
-        _hip.check(self._L.ds_scalar_csr_spmm(pp(ptr_), pp(col), pp(w), nrows, pp(X), _ld(X), pp(Y), _ld(Y),
-                                              X.shape[1], float(beta), _hip.stream_ptr()), "ds_scalar_csr_spmm")
+        _hip.launch("ds_scalar_csr_spmm", pp(ptr_), pp(col), pp(w), nrows, pp(X), _ld(X), pp(Y), _ld(Y), X.shape[1], float(beta))
 
     def restrict(self, Rf, Rc):
         """Rc <- P^T Rf (fine block -> corner-node level)."""
@@ -710,7 +695,7 @@ class _HipBlockOps:
         """out (fp64) <- A X for an fp64 block X, in chunks of <= 80 columns (kinds 4 / 5 of ds_spmm_bsr3)."""
         if X.dtype != torch.float64 or out.dtype != torch.float64 or X.shape != out.shape:
             raise ValueError("_spmm64: fp64 blocks of equal shape expected")
-        self._spmm_chunks(kind + 2, vals, None, X, out, 80, "ds_spmm_bsr3(f64)")
+        self._spmm_chunks(kind + 2, vals, None, X, out, 80)
 
     def combined_k64(self, on):
         """fp64 refinement: while ``on``, ``apply_K64`` multiplies by ONE fp64 block array K = sum c_i K_i, formed on the
@@ -740,8 +725,8 @@ class _HipBlockOps:
         tabs = self._union_tabs()
         for c0, c1 in self.col_slices(X.shape[1]):
             xs, os_ = X[:, c0:c1], out[:, c0:c1]
-            _hip.check(self._L.ds_spmm_f64_union(kind, 1, *tabs, pp(vals_grp), vals_grp.shape[0], self.nv, pp(xs), _ld(xs),
-                                                 pp(os_), _ld(os_), c1 - c0, _hip.stream_ptr()), "ds_spmm_f64_union")
+            _hip.launch("ds_spmm_f64_union", kind, 1, *tabs, pp(vals_grp), vals_grp.shape[0], self.nv, pp(xs), _ld(xs), pp(os_), _ld(os_),
+                        c1 - c0)
 
     def apply_K64(self, X, out, terms=False):
         """out <- K X, all fp64 (fp64 block values).  ``terms``: also return the list of the separate K_i X."""
@@ -815,9 +800,9 @@ class _HipBlockOps:
             return None
         Y3 = block((X.shape[0], 3 * c))
         p = _hip.ptr
-        fn = self._L.ds_spmm_f64_polish if Y3.dtype == torch.float64 else self._L.ds_spmm_f64_polish_f32out
-        _hip.check(fn(p(self.rowptr), p(self.colidx), p(kterms[0][1]), p(kterms[1][1]), p(mvals), self.nv, p(X), _ld(X),
-                      p(Y3[:, :c]), p(Y3[:, c:2 * c]), p(Y3[:, 2 * c:]), 3 * c, c, _hip.stream_ptr()), "ds_spmm_f64_polish")
+        _hip.launch("ds_spmm_f64_polish" if Y3.dtype == torch.float64 else "ds_spmm_f64_polish_f32out", p(self.rowptr), p(self.colidx),
+                    p(kterms[0][1]), p(kterms[1][1]), p(mvals), self.nv, p(X), _ld(X), p(Y3[:, :c]), p(Y3[:, c:2 * c]), p(Y3[:, 2 * c:]),
+                    3 * c, c)
         return Y3
 
     def polish_products(self, X):

@@ -37,12 +37,6 @@ def _restore(ctx, gy):
     return d, w, (amp if ctx.has_amp else None), force, gy.float().contiguous()
 
 
-def _work(query, *dims, device):
-    """The workspace of a recursive bank: ``query`` is its ds_osc_*_workspace_bytes, ``dims`` that query's arguments."""
-    nbytes = query(*dims)
-    return torch.empty(nbytes, dtype=torch.uint8, device=device), nbytes
-
-
 def _grad_buffers(d, w, amp):
     """Uninitialised gradients of d, w and, where there is one, amp: the kernels write every element."""
     return torch.empty_like(d), torch.empty_like(w), (None if amp is None else torch.empty_like(amp))
@@ -57,8 +51,7 @@ class _OscBank(torch.autograd.Function):
         A, nF = force.shape
         y = torch.empty((A, S), dtype=torch.float32, device=force.device)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_osc_bank_fwd(p(d), p(w), p(amp), p(force), A, d.shape[0], nF, S, float(sr), p(y),
-                                              _hip.stream_ptr()), "ds_osc_bank_fwd")
+        _hip.launch("ds_osc_bank_fwd", p(d), p(w), p(amp), p(force), A, d.shape[0], nF, S, float(sr), p(y), device=d.device)
         _save(ctx, d, w, amp, force, S, sr)
         return y
 
@@ -69,8 +62,8 @@ class _OscBank(torch.autograd.Function):
         gs = torch.empty_like(gy)
         gd, gw, gamp = _grad_buffers(d, w, amp)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_osc_bank_bwd(p(gy), p(d), p(w), p(amp), p(force), A, d.shape[0], nF, ctx.S, ctx.sr, p(gs),
-                                              p(gd), p(gw), p(gamp), _hip.stream_ptr()), "ds_osc_bank_bwd")
+        _hip.launch("ds_osc_bank_bwd", p(gy), p(d), p(w), p(amp), p(force), A, d.shape[0], nF, ctx.S, ctx.sr, p(gs), p(gd), p(gw),
+                    p(gamp), device=d.device)
         return gd, gw, gamp, None, None, None
 
 
@@ -83,12 +76,11 @@ class _OscBankTV(torch.autograd.Function):
         A, m, S_ = dmp.shape
         if S_ != S or frq.shape != dmp.shape or force.shape[0] != A:
             raise ValueError("time-varying bank: dmp and frq must be (audio_num, mode_num, sample_num)")
-        L = _hip.lib()
-        work = torch.empty(L.ds_osc_tv_workspace_floats(A, m, S), dtype=torch.float32, device=dmp.device)
+        work, _ = _hip.workspace("ds_osc_tv_workspace_floats", A, m, S, device=dmp.device, dtype=torch.float32)
         y = torch.empty((A, S), dtype=torch.float32, device=dmp.device)
         p = _hip.ptr
-        _hip.check(L.ds_osc_tv_fwd(p(dmp), p(frq), p(amp), p(force), A, m, force.shape[1], S, float(sr), p(work), p(y),
-                                   _hip.stream_ptr()), "ds_osc_tv_fwd")
+        _hip.launch("ds_osc_tv_fwd", p(dmp), p(frq), p(amp), p(force), A, m, force.shape[1], S, float(sr), p(work), p(y),
+                    device=dmp.device)
         _save(ctx, dmp, frq, amp, force, S, sr)
         return y
 
@@ -99,8 +91,8 @@ class _OscBankTV(torch.autograd.Function):
         gs = torch.empty_like(gy)
         gd, gf, gamp = _grad_buffers(dmp, frq, amp)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_osc_tv_bwd(p(gy), p(dmp), p(frq), p(amp), p(force), A, m, force.shape[1], S, ctx.sr,
-                                            p(gs), p(gd), p(gf), p(gamp), _hip.stream_ptr()), "ds_osc_tv_bwd")
+        _hip.launch("ds_osc_tv_bwd", p(gy), p(dmp), p(frq), p(amp), p(force), A, m, force.shape[1], S, ctx.sr, p(gs), p(gd), p(gf),
+                    p(gamp), device=dmp.device)
         return gd, gf, gamp, None, None, None
 
 
@@ -113,12 +105,10 @@ class _OscDriven(torch.autograd.Function):
         d, w, amp, force = _prepare(torch.float64, d, w, amp, force)
         A, nF = force.shape
         m = d.shape[0]
-        L = _hip.lib()
-        work, nbytes = _work(L.ds_osc_driven_workspace_bytes, A, m, S, device=force.device)
+        work, nbytes = _hip.workspace("ds_osc_driven_workspace_bytes", A, m, S, device=d.device)
         y = torch.empty((A, S), dtype=torch.float32, device=force.device)
         p = _hip.ptr
-        _hip.check(L.ds_osc_driven_fwd(p(d), p(w), p(amp), p(force), A, m, nF, S, float(sr), p(work), nbytes, p(y),
-                                       _hip.stream_ptr()), "ds_osc_driven_fwd")
+        _hip.launch("ds_osc_driven_fwd", p(d), p(w), p(amp), p(force), A, m, nF, S, float(sr), p(work), nbytes, p(y), device=d.device)
         _save(ctx, d, w, amp, force, S, sr)
         return y
 
@@ -127,13 +117,12 @@ class _OscDriven(torch.autograd.Function):
         d, w, amp, force, gy = _restore(ctx, gy)
         A, nF = force.shape
         m = d.shape[0]
-        L = _hip.lib()
-        work, nbytes = _work(L.ds_osc_driven_workspace_bytes, A, m, ctx.S, device=gy.device)
+        work, nbytes = _hip.workspace("ds_osc_driven_workspace_bytes", A, m, ctx.S, device=d.device)
         gd, gw, gamp = _grad_buffers(d, w, amp)
         gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
         p = _hip.ptr
-        _hip.check(L.ds_osc_driven_bwd(p(gy), p(d), p(w), p(amp), p(force), A, m, nF, ctx.S, ctx.sr, p(work), nbytes, p(gd),
-                                       p(gw), p(gamp), p(gforce), _hip.stream_ptr()), "ds_osc_driven_bwd")
+        _hip.launch("ds_osc_driven_bwd", p(gy), p(d), p(w), p(amp), p(force), A, m, nF, ctx.S, ctx.sr, p(work), nbytes, p(gd), p(gw),
+                    p(gamp), p(gforce), device=d.device)
         return gd, gw, gamp, gforce, None, None
 
 
@@ -154,12 +143,11 @@ class _OscSliding(torch.autograd.Function):
             raise ValueError(f"sliding bank: hop = {hop} is not a positive multiple of {SLIDE_HOP_UNIT}")
         K = gain.shape[1]
         gain_k = gain.detach().float().transpose(1, 2).contiguous()  # the kernels' layout: (A, m, K), frames contiguous
-        L = _hip.lib()
-        work, nbytes = _work(L.ds_osc_slide_workspace_bytes, A, m, S, K, hop, device=force.device)
+        work, nbytes = _hip.workspace("ds_osc_slide_workspace_bytes", A, m, S, K, hop, device=d.device)
         y = torch.empty((A, S), dtype=torch.float32, device=force.device)
         p = _hip.ptr
-        _hip.check(L.ds_osc_slide_fwd(p(d), p(w), p(amp), p(force), p(gain_k), A, m, nF, S, K, hop, float(sr), p(work), nbytes,
-                                      p(y), _hip.stream_ptr()), "ds_osc_slide_fwd")
+        _hip.launch("ds_osc_slide_fwd", p(d), p(w), p(amp), p(force), p(gain_k), A, m, nF, S, K, hop, float(sr), p(work), nbytes,
+                    p(y), device=d.device)
         _save(ctx, d, w, amp, force, S, sr)
         ctx.gain_k, ctx.hop, ctx.gain_dtype = gain_k, hop, gain.dtype
         return y
@@ -170,15 +158,13 @@ class _OscSliding(torch.autograd.Function):
         gain_k, hop = ctx.gain_k, ctx.hop
         A, nF = force.shape
         m, K = d.shape[0], gain_k.shape[2]
-        L = _hip.lib()
-        work, nbytes = _work(L.ds_osc_slide_workspace_bytes, A, m, ctx.S, K, hop, device=gy.device)
+        work, nbytes = _hip.workspace("ds_osc_slide_workspace_bytes", A, m, ctx.S, K, hop, device=d.device)
         gd, gw, gamp = _grad_buffers(d, w, amp)
         gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
         ggain = torch.empty_like(gain_k) if ctx.needs_input_grad[4] else None
         p = _hip.ptr
-        _hip.check(L.ds_osc_slide_bwd(p(gy), p(d), p(w), p(amp), p(force), p(gain_k), A, m, nF, ctx.S, K, hop, ctx.sr, p(work),
-                                      nbytes, p(gd), p(gw), p(gamp), p(gforce), p(ggain), _hip.stream_ptr()),
-                   "ds_osc_slide_bwd")
+        _hip.launch("ds_osc_slide_bwd", p(gy), p(d), p(w), p(amp), p(force), p(gain_k), A, m, nF, ctx.S, K, hop, ctx.sr, p(work),
+                    nbytes, p(gd), p(gw), p(gamp), p(gforce), p(ggain), device=d.device)
         if ggain is not None:
             ggain = ggain.transpose(1, 2).to(ctx.gain_dtype)
         return gd, gw, gamp, gforce, ggain, None, None, None
@@ -216,12 +202,11 @@ class _OscListener(torch.autograd.Function):
         C, K = hgain.shape[1], hgain.shape[3]
         # the kernels' layout: (A, C, m, K, 2); a gain built as t.conj() carries torch's lazy conjugate bit, which view_as_real refuses
         h = torch.view_as_real(hgain.detach().to(torch.complex64).resolve_conj().contiguous())
-        L = _hip.lib()
-        work, nbytes = _work(L.ds_osc_listen_workspace_bytes, A, C, m, S, K, hop, device=force.device)
+        work, nbytes = _hip.workspace("ds_osc_listen_workspace_bytes", A, C, m, S, K, hop, device=d.device)
         y = torch.empty((A, C, S), dtype=torch.float32, device=force.device)
         p = _hip.ptr
-        _hip.check(L.ds_osc_listen_fwd(p(d), p(w), p(amp), p(force), p(h), A, C, m, nF, S, K, hop, float(sr), p(work), nbytes,
-                                       p(y), _hip.stream_ptr()), "ds_osc_listen_fwd")
+        _hip.launch("ds_osc_listen_fwd", p(d), p(w), p(amp), p(force), p(h), A, C, m, nF, S, K, hop, float(sr), p(work), nbytes,
+                    p(y), device=d.device)
         _save(ctx, d, w, amp, force, S, sr)
         ctx.h, ctx.hop, ctx.h_dtype = h, hop, hgain.dtype
         return y
@@ -232,15 +217,13 @@ class _OscListener(torch.autograd.Function):
         h, hop = ctx.h, ctx.hop
         A, nF = force.shape
         m, C, K = d.shape[0], h.shape[1], h.shape[3]
-        L = _hip.lib()
-        work, nbytes = _work(L.ds_osc_listen_workspace_bytes, A, C, m, ctx.S, K, hop, device=gy.device)
+        work, nbytes = _hip.workspace("ds_osc_listen_workspace_bytes", A, C, m, ctx.S, K, hop, device=d.device)
         gd, gw, gamp = _grad_buffers(d, w, amp)
         gforce = torch.empty_like(force) if ctx.needs_input_grad[3] else None
         gh = torch.empty_like(h) if ctx.needs_input_grad[4] else None
         p = _hip.ptr
-        _hip.check(L.ds_osc_listen_bwd(p(gy), p(d), p(w), p(amp), p(force), p(h), A, C, m, nF, ctx.S, K, hop, ctx.sr, p(work),
-                                       nbytes, p(gd), p(gw), p(gamp), p(gforce), p(gh), _hip.stream_ptr()),
-                   "ds_osc_listen_bwd")
+        _hip.launch("ds_osc_listen_bwd", p(gy), p(d), p(w), p(amp), p(force), p(h), A, C, m, nF, ctx.S, K, hop, ctx.sr, p(work),
+                    nbytes, p(gd), p(gw), p(gamp), p(gforce), p(gh), device=d.device)
         if gh is not None:  # (d loss / d Re h, d loss / d Im h) is the gradient of a real loss as torch keeps it for a complex leaf
             gh = torch.view_as_complex(gh).to(ctx.h_dtype)
         return gd, gw, gamp, gforce, gh, None, None, None

@@ -30,8 +30,7 @@ class _Biquad(torch.autograd.Function):
         S, per_clip = sos.shape[-2], int(sos.dim() == 3)
         y = torch.empty_like(x)
         p = _hip.ptr
-        with torch.cuda.device(x.device):
-            _hip.check(_hip.lib().ds_biquad_fwd(p(x), p(sos), per_clip, B, N, S, p(y), _hip.stream_ptr()), "ds_biquad_fwd")
+        _hip.launch("ds_biquad_fwd", p(x), p(sos), per_clip, B, N, S, p(y), device=x.device)
         ctx.save_for_backward(x, sos)
         return y
 
@@ -43,15 +42,11 @@ class _Biquad(torch.autograd.Function):
         B, N = x.shape
         S, per_clip = sos.shape[-2], int(sos.dim() == 3)
         gy = gy.float().contiguous()
-        L = _hip.lib()
-        nbytes = L.ds_biquad_workspace_bytes(B, N, S)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        work, nbytes = _hip.workspace("ds_biquad_workspace_bytes", B, N, S, device=x.device)
         gx = torch.empty_like(x)
         gsos = torch.empty((B, S, 5), dtype=torch.float64, device=x.device)
         p = _hip.ptr
-        with torch.cuda.device(x.device):
-            _hip.check(L.ds_biquad_bwd(p(gy), p(x), p(sos), per_clip, B, N, S, p(work), nbytes, p(gx), p(gsos),
-                                       _hip.stream_ptr()), "ds_biquad_bwd")
+        _hip.launch("ds_biquad_bwd", p(gy), p(x), p(sos), per_clip, B, N, S, p(work), nbytes, p(gx), p(gsos), device=x.device)
         return gx, (gsos if per_clip else gsos.sum(0))
 
 

@@ -62,8 +62,7 @@ class _ContactForce(torch.autograd.Function):
         A, m = ops[2].shape
         force = torch.empty((A, force_len), dtype=torch.float32, device=d.device)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_contact_fwd(*map(p, ops), A, m, force_len, oversample, exponent, sr, p(force),
-                                             _hip.stream_ptr()), "ds_contact_fwd")
+        _hip.launch("ds_contact_fwd", *map(p, ops), A, m, force_len, oversample, exponent, sr, p(force), device=d.device)
         ctx.save_for_backward(*ops)
         ctx.args = (force_len, sr, exponent, oversample)
         ctx.dtypes = tuple(t.dtype for t in (d, w, gain, mass, velocity, stiffness))
@@ -80,13 +79,11 @@ class _ContactForce(torch.autograd.Function):
         ggain = new(ops[2], need[2])
         hammer = need[3] or need[4] or need[5]
         gmass, gvel, gstiff = new(ops[3], hammer), new(ops[4], hammer), new(ops[5], hammer)
-        L = _hip.lib()
-        nbytes = L.ds_contact_workspace_bytes(A, m, F, R)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=gforce.device)
+        work, nbytes = _hip.workspace("ds_contact_workspace_bytes", A, m, F, R, device=gforce.device)
         gforce = gforce.float().contiguous()
         p = _hip.ptr
-        _hip.check(L.ds_contact_bwd(p(gforce), *map(p, ops), A, m, F, R, exponent, sr, p(work), nbytes,
-                                    p(gd), p(gw), p(ggain), p(gmass), p(gvel), p(gstiff), _hip.stream_ptr()), "ds_contact_bwd")
+        _hip.launch("ds_contact_bwd", p(gforce), *map(p, ops), A, m, F, R, exponent, sr, p(work), nbytes, p(gd), p(gw), p(ggain),
+                    p(gmass), p(gvel), p(gstiff), device=gforce.device)
         grads = (gd, gw, ggain, gmass, gvel, gstiff)
         return tuple(g.to(dt) if g is not None and on else None for g, dt, on in zip(grads, ctx.dtypes, need)) + (None,) * 4
 

@@ -30,8 +30,7 @@ class _Delay(torch.autograd.Function):
         B, S = s.shape
         y = torch.empty_like(s)
         p = _hip.ptr
-        with torch.cuda.device(s.device):
-            _hip.check(_hip.lib().ds_delay_fwd(p(s), p(tau), B, S, tau.shape[1], hop, p(y), _hip.stream_ptr()), "ds_delay_fwd")
+        _hip.launch("ds_delay_fwd", p(s), p(tau), B, S, tau.shape[1], hop, p(y), device=s.device)
         ctx.save_for_backward(s, tau)
         ctx.hop = hop
         return y
@@ -45,15 +44,11 @@ class _Delay(torch.autograd.Function):
         B, S = s.shape
         K = tau.shape[1]
         gy = gy.float().contiguous()
-        L = _hip.lib()
-        nbytes = L.ds_delay_workspace_bytes(B, S, K, ctx.hop)
-        work = torch.empty(nbytes, dtype=torch.uint8, device=s.device)
+        work, nbytes = _hip.workspace("ds_delay_workspace_bytes", B, S, K, ctx.hop, device=s.device)
         gs = torch.empty_like(s) if need_s else None
         gtau = torch.empty_like(tau) if need_t else None
         p = _hip.ptr
-        with torch.cuda.device(s.device):
-            _hip.check(L.ds_delay_bwd(p(gy), p(s), p(tau), B, S, K, ctx.hop, p(work), nbytes, p(gs), p(gtau), _hip.stream_ptr()),
-                       "ds_delay_bwd")
+        _hip.launch("ds_delay_bwd", p(gy), p(s), p(tau), B, S, K, ctx.hop, p(work), nbytes, p(gs), p(gtau), device=s.device)
         return gs, gtau, None
 
 

@@ -43,8 +43,7 @@ class _FilteredNoiseFn(torch.autograd.Function):
                              f"(noise_num, {S // frame_length + 1}, filter_coeff_length / {frame_length})")
         out = torch.empty((B, S), dtype=torch.float32, device=bank.device)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_filtered_noise_fwd(p(bank), p(noise), B, S, L, frame_length, float(gain), p(out),
-                                                    _hip.stream_ptr()), "ds_filtered_noise_fwd")
+        _hip.launch("ds_filtered_noise_fwd", p(bank), p(noise), B, S, L, frame_length, float(gain), p(out), device=bank.device)
         ctx.save_for_backward(bank, noise)
         ctx.S, ctx.frame_length, ctx.gain = S, frame_length, float(gain)
         return out
@@ -56,8 +55,8 @@ class _FilteredNoiseFn(torch.autograd.Function):
         gy = gy.float().contiguous()
         gc = torch.empty_like(bank)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_filtered_noise_bwd(p(gy), p(bank), p(noise), B, ctx.S, L, ctx.frame_length, ctx.gain, p(gc),
-                                                    _hip.stream_ptr()), "ds_filtered_noise_bwd")
+        _hip.launch("ds_filtered_noise_bwd", p(gy), p(bank), p(noise), B, ctx.S, L, ctx.frame_length, ctx.gain, p(gc),
+                    device=bank.device)
         return gc, None, None, None, None
 
 

@@ -107,7 +107,7 @@ def stft_power(x, n_fft, hop, keep_parts=False):
     re = torch.empty_like(P) if keep_parts else None
     im = torch.empty_like(P) if keep_parts else None
     p = _hip.ptr
-    _hip.check(_hip.lib().ds_stft_power(p(x), B, S, n_fft, hop, p(P), p(re), p(im), _hip.stream_ptr()), "ds_stft_power")
+    _hip.launch("ds_stft_power", p(x), B, S, n_fft, hop, p(P), p(re), p(im), device=x.device)
     return (P, re, im) if keep_parts else P
 
 
@@ -128,8 +128,7 @@ class _SpecLoss(torch.autograd.Function):
         sums = torch.empty((B, F_, 2), dtype=torch.float64, device=Pp.device)
         gP = torch.empty_like(Pp) if need_grad else None
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_spec_loss(kind, p(Pp), p(Pt), B, F_, T, float(alpha), float(eps), fclip, p(sums), p(gP),
-                                           _hip.stream_ptr()), "ds_spec_loss")
+        _hip.launch("ds_spec_loss", kind, p(Pp), p(Pt), B, F_, T, float(alpha), float(eps), fclip, p(sums), p(gP), device=Pp.device)
         tot = sums.sum((0, 1))
         if kind == 0:
             loss = (alpha * tot[0] + tot[1]) / (B * (F_ - 1) * T)
@@ -151,8 +150,7 @@ class _SpecLoss(torch.autograd.Function):
         gframes = torch.empty((B, T, n_fft), dtype=torch.float32, device=gP.device)
         gx = torch.empty((B, S), dtype=torch.float32, device=gP.device)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_stft_power_bwd(p(gP), p(re), p(im), B, S, n_fft, hop, 1.0, p(gframes), p(gx),
-                                                _hip.stream_ptr()), "ds_stft_power_bwd")
+        _hip.launch("ds_stft_power_bwd", p(gP), p(re), p(im), B, S, n_fft, hop, 1.0, p(gframes), p(gx), device=gP.device)
         gx = gx * gscale.float()  # the upstream gradient stays on the device: no host synchronisation in backward
         return (gx if xdim == 2 else gx[0]), None, None, None, None, None, None, None
 

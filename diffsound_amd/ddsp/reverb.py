@@ -29,8 +29,7 @@ class _Fir(torch.autograd.Function):
         (B, N), (H, L) = x.shape, h.shape
         y = torch.empty_like(x)
         p = _hip.ptr
-        with torch.cuda.device(x.device):
-            _hip.check(_hip.lib().ds_fir_fwd(p(x), p(h), B, H, N, L, p(y), _hip.stream_ptr()), "ds_fir_fwd")
+        _hip.launch("ds_fir_fwd", p(x), p(h), B, H, N, L, p(y), device=x.device)
         ctx.save_for_backward(x, h)
         return y
 
@@ -42,15 +41,11 @@ class _Fir(torch.autograd.Function):
             return None, None
         (B, N), (H, L) = x.shape, h.shape
         gy = gy.float().contiguous()
-        lib = _hip.lib()
-        nbytes = lib.ds_fir_workspace_bytes(B, H, N, L) if need_h else 0
-        work = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if need_h else None
+        work, nbytes = _hip.workspace("ds_fir_workspace_bytes", B, H, N, L, device=x.device) if need_h else (None, 0)
         gx = torch.empty_like(x) if need_x else None
         gh = torch.empty_like(h) if need_h else None
         p = _hip.ptr
-        with torch.cuda.device(x.device):
-            _hip.check(lib.ds_fir_bwd(p(gy), p(x), p(h), B, H, N, L, p(work), nbytes, p(gx), p(gh), _hip.stream_ptr()),
-                       "ds_fir_bwd")
+        _hip.launch("ds_fir_bwd", p(gy), p(x), p(h), B, H, N, L, p(work), nbytes, p(gx), p(gh), device=x.device)
         return gx, gh
 
 

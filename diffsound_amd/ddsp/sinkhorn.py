@@ -87,8 +87,7 @@ def _bbox_record(x, y, a, b):
     B, N, D = x.shape
     M = y.shape[1]
     out = torch.empty(3 * D + 3, dtype=torch.float32, device=x.device)
-    _hip.check(_hip.lib().ds_sinkhorn_bbox(x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), B, N, M, D,
-                                           out.data_ptr(), _hip.stream_ptr()), "ds_sinkhorn_bbox")
+    _hip.launch("ds_sinkhorn_bbox", x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), B, N, M, D, out.data_ptr(), device=x.device)
     r = out.cpu().numpy().astype(np.float64)
     if r[2 * D + 2:].sum() > 0:
         raise ValueError("sinkhorn: coordinates and weights must be finite")
@@ -110,8 +109,7 @@ def schedule(x, y, a=None, b=None, blur=0.05, scaling=0.5, diameter=None):
     """(diameter, eps_list) that ``sinkhorn_divergence`` uses on these inputs."""
     _check_options(blur, scaling, diameter)
     x, y, a, b, _ = _prepare(x, y, a, b)
-    with torch.cuda.device(x.device):
-        return _schedule(x, y, a, b, blur, scaling, diameter)
+    return _schedule(x, y, a, b, blur, scaling, diameter)
 
 
 class _Sinkhorn(torch.autograd.Function):
@@ -121,18 +119,15 @@ class _Sinkhorn(torch.autograd.Function):
     def forward(ctx, x, y, a, b, eps_list, debias):
         B, N, D = x.shape
         M = y.shape[1]
-        lib = _hip.lib()
-        nw = lib.ds_sinkhorn_workspace_floats(B, N, M)
+        nw = _hip.lib().ds_sinkhorn_workspace_floats(B, N, M)  # (not _hip.workspace: a negative answer is this query's refusal)
         if nw < 0:
             raise ValueError(f"sinkhorn: sizes out of range B={B} N={N} M={M}")
         work = torch.empty(nw, dtype=torch.float32, device=x.device)
         loss = torch.empty(B, dtype=torch.float64, device=x.device)
         eps = (ctypes.c_float * len(eps_list))(*eps_list)
-        st = _hip.stream_ptr()
         args = (x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), B, N, M, D)
-        _hip.check(lib.ds_sinkhorn_loop(*args, eps, len(eps_list), int(debias), work.data_ptr(), st), "ds_sinkhorn_loop")
-        _hip.check(lib.ds_sinkhorn_final(*args, float(eps_list[-1]), int(debias), work.data_ptr(), loss.data_ptr(), st),
-                   "ds_sinkhorn_final")
+        _hip.launch("ds_sinkhorn_loop", *args, eps, len(eps_list), int(debias), work.data_ptr(), device=x.device)
+        _hip.launch("ds_sinkhorn_final", *args, float(eps_list[-1]), int(debias), work.data_ptr(), loss.data_ptr(), device=x.device)
         ctx.save_for_backward(x, y, a, b, work)
         ctx.meta = (float(eps_list[-1]), int(debias))
         return loss.float()
@@ -148,9 +143,8 @@ class _Sinkhorn(torch.autograd.Function):
         if gx is None and gy is None:
             return (None,) * 6
         g = g.detach().float().contiguous()
-        _hip.check(_hip.lib().ds_sinkhorn_backward(x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), B, N, M, D,
-                                                   eps, debias, work.data_ptr(), g.data_ptr(), _hip.ptr(gx),
-                                                   _hip.ptr(gy), _hip.stream_ptr()), "ds_sinkhorn_backward")
+        _hip.launch("ds_sinkhorn_backward", x.data_ptr(), y.data_ptr(), a.data_ptr(), b.data_ptr(), B, N, M, D, eps, debias,
+                    work.data_ptr(), g.data_ptr(), _hip.ptr(gx), _hip.ptr(gy), device=x.device)
         return gx, gy, None, None, None, None
 
 
@@ -160,9 +154,8 @@ def sinkhorn_divergence(x, y, a=None, b=None, blur=0.05, scaling=0.5, diameter=N
     uniform when None.  Returns a scalar, or (B,) for batched input.  ``debias=False`` gives <a, f_ba> + <b, g_ab>."""
     _check_options(blur, scaling, diameter)
     xf, yf, af, bf, batched = _prepare(x, y, a, b)
-    with torch.cuda.device(xf.device):
-        _, eps_list = _schedule(xf, yf, af, bf, blur, scaling, diameter)
-        S = _Sinkhorn.apply(xf, yf, af, bf, eps_list, bool(debias))
+    _, eps_list = _schedule(xf, yf, af, bf, blur, scaling, diameter)
+    S = _Sinkhorn.apply(xf, yf, af, bf, eps_list, bool(debias))
     return S if batched else S[0]
 
 

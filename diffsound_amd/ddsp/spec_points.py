@@ -42,8 +42,7 @@ class _SpecPoints(torch.autograd.Function):
         win = None if freq is None else torch.empty(F_ + fclip, dtype=torch.int64, device=P.device)
         E = 0 if freq is None else freq.numel()
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_spec_points_fwd(p(P), B, F_, T, eps, fclip, p(freq), E, sample_rate, p(win), p(lin), p(log),
-                                                 _hip.stream_ptr()), "ds_spec_points_fwd")
+        _hip.launch("ds_spec_points_fwd", p(P), B, F_, T, eps, fclip, p(freq), E, sample_rate, p(win), p(lin), p(log), device=P.device)
         if freq is not None:
             ctx.save_for_backward(freq, win)
         ctx.meta = (B, F_, fclip, sample_rate, copies)
@@ -59,8 +58,8 @@ class _SpecPoints(torch.autograd.Function):
         g_log = None if g_log is None else g_log.detach().float().contiguous()
         g_freq = torch.empty_like(freq)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_spec_points_bwd(p(g_lin), p(g_log), B, F_, fclip, p(freq), freq.numel(), sample_rate, p(win),
-                                                 float(copies), p(g_freq), _hip.stream_ptr()), "ds_spec_points_bwd")
+        _hip.launch("ds_spec_points_bwd", p(g_lin), p(g_log), B, F_, fclip, p(freq), freq.numel(), sample_rate, p(win), float(copies),
+                    p(g_freq), device=freq.device)
         return None, g_freq, None, None, None, None
 
 
@@ -94,5 +93,4 @@ def spectral_points(P, freq=None, sample_rate=None, scale=1.0, eps=1e-7):
         total = freq.numel()
         freq = collapse_expanded(freq).reshape(-1).float().contiguous()
         copies = total // freq.numel()  # every kept entry stands for this many equal ones
-    with torch.cuda.device(P.device):
-        return _SpecPoints.apply(P, freq, 0 if freq is None else int(sample_rate), fclip, float(eps), copies)
+    return _SpecPoints.apply(P, freq, 0 if freq is None else int(sample_rate), fclip, float(eps), copies)

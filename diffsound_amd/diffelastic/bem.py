@@ -144,12 +144,10 @@ class BEMModel:
         self._tris = t[perm].to(torch.int32).contiguous()
         self._verts = v
         self.rec = torch.empty((m, FACE_RECORD), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_bem_geometry(v.data_ptr(), v.shape[0], self._tris.data_ptr(), m, self.rec.data_ptr(),
-                                                  _hip.stream_ptr()), "ds_bem_geometry")
+        _hip.launch("ds_bem_geometry", v.data_ptr(), v.shape[0], self._tris.data_ptr(), m, self.rec.data_ptr(), device=self.device)
         self.area = self.rec[:, 31].contiguous()
         self._inv_area = (1.0 / self.area).contiguous()
-        self._work = torch.empty(int(_hip.lib().ds_bem_assemble_workspace_bytes(m)), dtype=torch.uint8, device=self.device)
+        self._work, _ = _hip.workspace("ds_bem_assemble_workspace_bytes", m, device=self.device)
         self._g = None
         self._u = None
 
@@ -188,18 +186,14 @@ class BEMModel:
         A = torch.empty((m, lda), dtype=torch.complex64, device=self.device)
         V = torch.empty((m, lda), dtype=torch.complex64, device=self.device) if want_V else None
         rhs = torch.empty(m, dtype=torch.complex64, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_bem_assemble(self.rec.data_ptr(), m, k, g_internal.data_ptr(), A.data_ptr(), lda,
-                                                  _hip.ptr(V), lda, rhs.data_ptr(), self._work.data_ptr(), _hip.stream_ptr()),
-                       "ds_bem_assemble")
+        _hip.launch("ds_bem_assemble", self.rec.data_ptr(), m, k, g_internal.data_ptr(), A.data_ptr(), lda, _hip.ptr(V), lda,
+                    rhs.data_ptr(), self._work.data_ptr(), device=self.device)
         return A, rhs, V
 
     def cgemv(self, A, x, scale=None, out=None):
         """y = diag(scale) A x (ds_bem_cgemv); x a 16-byte aligned complex64 vector of length >= m."""
         y = out if out is not None else torch.empty(self.m, dtype=torch.complex64, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_bem_cgemv(A.data_ptr(), A.stride(0), x.data_ptr(), self.m, _hip.ptr(scale), y.data_ptr(),
-                                               _hip.stream_ptr()), "ds_bem_cgemv")
+        _hip.launch("ds_bem_cgemv", A.data_ptr(), A.stride(0), x.data_ptr(), self.m, _hip.ptr(scale), y.data_ptr(), device=self.device)
         return y
 
     def _potential(self, k, g, u, points):
@@ -214,9 +208,8 @@ class BEMModel:
         if not bool(torch.isfinite(p).all()):
             raise ValueError("potential_solve: points hold non-finite coordinates")
         out = torch.empty(p.shape[0], dtype=torch.complex64, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_bem_potential(self.rec.data_ptr(), self.m, k, g.data_ptr(), u.data_ptr(), p.data_ptr(),
-                                                   p.shape[0], out.data_ptr(), _hip.stream_ptr()), "ds_bem_potential")
+        _hip.launch("ds_bem_potential", self.rec.data_ptr(), self.m, k, g.data_ptr(), u.data_ptr(), p.data_ptr(), p.shape[0],
+                    out.data_ptr(), device=self.device)
         return out
 
     # ------------------------------------------------------------------ GMRES

@@ -132,9 +132,7 @@ class Deform:
 
     def _tables(self, sfd=None, intw=None, det=None):
         v, args = self._mesh_args()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_deform_tables(*args, _hip.ptr(sfd), _hip.ptr(intw), _hip.ptr(det),
-                                                   _hip.stream_ptr()), "ds_deform_tables")
+        _hip.launch("ds_deform_tables", *args, _hip.ptr(sfd), _hip.ptr(intw), _hip.ptr(det), device=self.device)
 
     def _gradient(self, u, weighted):
         nv = self.tetmesh.vertices.shape[0]
@@ -145,9 +143,7 @@ class Deform:
         u = u.detach().float().contiguous()
         F = torch.empty((u.shape[0], self.num_tets * self.num_guass_points, 3, 3), dtype=torch.float32, device=self.device)
         v, args = self._mesh_args()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_deform_gradient(*args, _hip.ptr(u), u.shape[0], int(bool(weighted)), _hip.ptr(F),
-                                                     _hip.stream_ptr()), "ds_deform_gradient")
+        _hip.launch("ds_deform_gradient", *args, _hip.ptr(u), u.shape[0], int(bool(weighted)), _hip.ptr(F), device=self.device)
         return F
 
     def _force(self, stress, weighted):
@@ -161,10 +157,8 @@ class Deform:
         f = torch.empty((batch, 3 * nv), dtype=torch.float32, device=self.device)
         work = torch.empty(batch * self.num_tets * self.num_nodes_per_tet * 3, dtype=torch.float32, device=self.device)
         v, args = self._mesh_args()
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_deform_force(*args, _hip.ptr(self._inc_ptr), _hip.ptr(self._inc), _hip.ptr(P), batch,
-                                                  int(bool(weighted)), _hip.ptr(work), _hip.ptr(f), _hip.stream_ptr()),
-                       "ds_deform_force")
+        _hip.launch("ds_deform_force", *args, _hip.ptr(self._inc_ptr), _hip.ptr(self._inc), _hip.ptr(P), batch, int(bool(weighted)),
+                    _hip.ptr(work), _hip.ptr(f), device=self.device)
         return f
 
     # ------------------------------------------------------------------ the reference's tables (lazy; not read above)

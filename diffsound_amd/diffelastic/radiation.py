@@ -70,9 +70,7 @@ class _Multipole(torch.autograd.Function):
         P, m = pts.shape[0], k.shape[0]
         out = torch.empty((P, m, 2), dtype=torch.float64, device=pts.device)
         p = _hip.ptr
-        with torch.cuda.device(pts.device):
-            _hip.check(_hip.lib().ds_multipole_fwd(p(pts), p(center), p(k), p(cf), P, m, order, p(out), _hip.stream_ptr()),
-                       "ds_multipole_fwd")
+        _hip.launch("ds_multipole_fwd", p(pts), p(center), p(k), p(cf), P, m, order, p(out), device=pts.device)
         ctx.save_for_backward(pts, cf, center, k)
         ctx.order = order
         ctx.dtypes = (points.dtype, coef2.dtype)
@@ -88,13 +86,10 @@ class _Multipole(torch.autograd.Function):
         gout = gout.to(torch.float64).contiguous()
         gpts = torch.empty_like(pts) if need_p else None
         gcf = torch.empty_like(cf) if need_c else None
-        lib = _hip.lib()
-        nbytes = lib.ds_multipole_workspace_bytes(P, m, L) if need_c else 0
-        work = torch.empty(nbytes, dtype=torch.uint8, device=pts.device) if need_c else None
+        work, nbytes = _hip.workspace("ds_multipole_workspace_bytes", P, m, L, device=pts.device) if need_c else (None, 0)
         p = _hip.ptr
-        with torch.cuda.device(pts.device):
-            _hip.check(lib.ds_multipole_bwd(p(gout), p(pts), p(center), p(k), p(cf), P, m, L, p(work), nbytes, p(gpts), p(gcf),
-                                            _hip.stream_ptr()), "ds_multipole_bwd")
+        _hip.launch("ds_multipole_bwd", p(gout), p(pts), p(center), p(k), p(cf), P, m, L, p(work), nbytes, p(gpts), p(gcf),
+                    device=pts.device)
         return (gpts.to(ctx.dtypes[0]) if need_p else None,
                 gcf.transpose(0, 1).to(ctx.dtypes[1]) if need_c else None, None, None, None)
 

@@ -111,7 +111,6 @@ class _MarchingTets(torch.autograd.Function):
     @staticmethod
     def forward(ctx, pos, sdf, thick, tab, want_faces):
         dev = pos.device
-        lib = _hip.lib()
         p = pos.contiguous()
         s = sdf.reshape(-1).contiguous()
         th = None if thick is None else thick.reshape(1).contiguous()
@@ -121,21 +120,19 @@ class _MarchingTets(torch.autograd.Function):
         vert_id = torch.empty(n, dtype=torch.int32, device=dev)
         work = torch.empty(tab.count_ws, dtype=torch.uint8, device=dev)
         c = _hip.MtCounts()
-        st = _hip.stream_ptr()
-        _hip.check(lib.ds_mt_count(s.data_ptr(), n, tab.tets.data_ptr(), T, tab.ea.data_ptr(), tab.eb.data_ptr(), E,
-                                   tab.vptr.data_ptr(), _hip.ptr(th), toff.data_ptr(), edge_id.data_ptr(),
-                                   vert_id.data_ptr(), work.data_ptr(), tab.count_ws, ctypes.byref(c), st), "ds_mt_count")
+        _hip.launch("ds_mt_count", s.data_ptr(), n, tab.tets.data_ptr(), T, tab.ea.data_ptr(), tab.eb.data_ptr(), E, tab.vptr.data_ptr(),
+                    _hip.ptr(th), toff.data_ptr(), edge_id.data_ptr(), vert_id.data_ptr(), work.data_ptr(), tab.count_ws,
+                    ctypes.byref(c), device=dev)
         nt = c.n_side1 + c.n_side3 + c.n_inner
         verts = torch.empty((c.n_used + c.n_cross, 3), dtype=torch.float32, device=dev)
         tets = torch.empty((nt, 4), dtype=torch.int64, device=dev)
         faces = torch.empty((c.n_face1 + c.n_face2 if want_faces else 0, 3), dtype=torch.int64, device=dev)
         vsrc = torch.empty(c.n_used, dtype=torch.int32, device=dev)
         xedge = torch.empty(c.n_cross, dtype=torch.int32, device=dev)
-        _hip.check(lib.ds_mt_emit(p.data_ptr(), s.data_ptr(), n, tab.tets.data_ptr(), T, tab.tet_edge.data_ptr(),
-                                  tab.ea.data_ptr(), tab.eb.data_ptr(), E, tab.vptr.data_ptr(), _hip.ptr(th),
-                                  toff.data_ptr(), edge_id.data_ptr(), vert_id.data_ptr(), ctypes.byref(c),
-                                  verts.data_ptr(), tets.data_ptr(), faces.data_ptr() if want_faces else None,
-                                  vsrc.data_ptr(), xedge.data_ptr(), st), "ds_mt_emit")
+        _hip.launch("ds_mt_emit", p.data_ptr(), s.data_ptr(), n, tab.tets.data_ptr(), T, tab.tet_edge.data_ptr(), tab.ea.data_ptr(),
+                    tab.eb.data_ptr(), E, tab.vptr.data_ptr(), _hip.ptr(th), toff.data_ptr(), edge_id.data_ptr(), vert_id.data_ptr(),
+                    ctypes.byref(c), verts.data_ptr(), tets.data_ptr(), faces.data_ptr() if want_faces else None, vsrc.data_ptr(),
+                    xedge.data_ptr(), device=dev)
         ctx.save_for_backward(p, s, th, edge_id, vert_id, xedge)
         ctx.tab, ctx.n_used, ctx.n_cross = tab, c.n_used, c.n_cross
         ctx.sdf_shape, ctx.thick_shape = sdf.shape, None if thick is None else thick.shape
@@ -151,16 +148,14 @@ class _MarchingTets(torch.autograd.Function):
         gv = torch.zeros((nout, 3), dtype=torch.float32, device=dev) if gv is None else gv.contiguous().float()
         dpos = torch.empty((n, 3), dtype=torch.float32, device=dev)
         dsdf = torch.empty(n, dtype=torch.float32, device=dev)
-        lib = _hip.lib()
         dt = work = None
         if th is not None:
             dt = torch.empty(1, dtype=torch.float32, device=dev)
-            work = torch.empty(int(lib.ds_mt_backward_workspace_floats(ctx.n_cross)), dtype=torch.float32, device=dev)
-        _hip.check(lib.ds_mt_backward(gv.data_ptr() if nout else None, p.data_ptr(), s.data_ptr(), n, tab.ea.data_ptr(),
-                                      tab.eb.data_ptr(), tab.E, tab.vptr.data_ptr(), tab.vadj.data_ptr(), _hip.ptr(th),
-                                      edge_id.data_ptr(), vert_id.data_ptr(), xedge.data_ptr() if ctx.n_cross else None,
-                                      ctx.n_used, ctx.n_cross, dpos.data_ptr(), dsdf.data_ptr(), _hip.ptr(dt),
-                                      _hip.ptr(work), _hip.stream_ptr()), "ds_mt_backward")
+            work, _ = _hip.workspace("ds_mt_backward_workspace_floats", ctx.n_cross, device=dev, dtype=torch.float32)
+        _hip.launch("ds_mt_backward", gv.data_ptr() if nout else None, p.data_ptr(), s.data_ptr(), n, tab.ea.data_ptr(),
+                    tab.eb.data_ptr(), tab.E, tab.vptr.data_ptr(), tab.vadj.data_ptr(), _hip.ptr(th), edge_id.data_ptr(),
+                    vert_id.data_ptr(), xedge.data_ptr() if ctx.n_cross else None, ctx.n_used, ctx.n_cross, dpos.data_ptr(),
+                    dsdf.data_ptr(), _hip.ptr(dt), _hip.ptr(work), device=dev)
         return dpos, dsdf.reshape(ctx.sdf_shape), None if dt is None else dt.reshape(ctx.thick_shape), None, None
 
 

@@ -114,9 +114,8 @@ class HipModalOps(_HipBlockOps):
         Y = torch.empty((X.shape[0], X.shape[1]), dtype=torch.float32, device=X.device)
         for c0 in range(0, X.shape[1], 256):
             c1 = min(X.shape[1], c0 + 256)
-            _hip.check(self._L.ds_group_apply16(_hip.ptr(self.tgrp), self.group_jacobi, X[:, c0:c1].data_ptr(), 1, _ld(X),
-                                                Y[:, c0:c1].data_ptr(), 1, _ld(Y), self.nv, c1 - c0, _hip.stream_ptr()),
-                       "ds_group_apply16")
+            _hip.launch("ds_group_apply16", _hip.ptr(self.tgrp), self.group_jacobi, X[:, c0:c1].data_ptr(), 1, _ld(X),
+                        Y[:, c0:c1].data_ptr(), 1, _ld(Y), self.nv, c1 - c0)
         return Y
 
     def probe_products(self, G0):
@@ -164,16 +163,14 @@ class HipModalOps(_HipBlockOps):
         p = _hip.ptr
         if C is None:
             self.tangent = self.k64c = None
-            _hip.check(self._L.ds_combine_material(p(s.klam), p(s.kmu), p(s.ms), s.nnzb, p(s.diagidx), s.nv, lame[0], lame[1],
-                                                   p(self.k32), p(self.k32t), p(self.ms32), p(self.dinv), _hip.stream_ptr()),
-                       "ds_combine_material")
+            _hip.launch("ds_combine_material", p(s.klam), p(s.kmu), p(s.ms), s.nnzb, p(s.diagidx), s.nv, lame[0], lame[1],
+                        p(self.k32), p(self.k32t), p(self.ms32), p(self.dinv))
         else:
             self.tangent = C.copy()
             if self.k64c is None:
                 self.k64c = torch.empty((s.nnzb, 9), dtype=torch.float64, device=self.device)
-            _hip.check(self._L.ds_combine_tangent(p(s.klam), p(s.ms), s.nnzb, p(s.diagidx), s.nv, C.ctypes.data, p(self.k64c),
-                                                  p(self.k32), p(self.k32t), p(self.ms32), p(self.dinv), _hip.stream_ptr()),
-                       "ds_combine_tangent")
+            _hip.launch("ds_combine_tangent", p(s.klam), p(s.ms), s.nnzb, p(s.diagidx), s.nv, C.ctypes.data, p(self.k64c),
+                        p(self.k32), p(self.k32t), p(self.ms32), p(self.dinv))
         self._after_combine(regen, gen)
 
     def tangent_forms(self, U):
@@ -182,11 +179,10 @@ class HipModalOps(_HipBlockOps):
         U = _mode_block(U, self.n, "tangent_forms")
         s, m = self.sys, U.shape[1]
         Q = torch.empty((m, 9, 9), dtype=torch.float64, device=self.device)
-        need = self._L.ds_tangent_forms_workspace_bytes(s.nv, m)
+        need = _hip.lib().ds_tangent_forms_workspace_bytes(s.nv, m)
         ws = self._scratch("tangent_forms_ws", ((need + 7) // 8,), torch.float64)
         p = _hip.ptr
-        _hip.check(self._L.ds_tangent_forms(p(s.rowptr), p(s.colidx), p(s.klam), s.nv, p(U), _ld(U), m, p(Q), p(ws),
-                                            ws.numel() * 8, _hip.stream_ptr()), "ds_tangent_forms")
+        _hip.launch("ds_tangent_forms", p(s.rowptr), p(s.colidx), p(s.klam), s.nv, p(U), _ld(U), m, p(Q), p(ws), ws.numel() * 8)
         return Q
 
     def geometry_grad(self, U, gk, gm):
@@ -204,15 +200,13 @@ class HipModalOps(_HipBlockOps):
         if s.groups is not None:
             if self.kgrp is None:
                 self.kgrp = torch.empty((s.nnzb, 9), dtype=torch.float32, device=self.device)
-            _hip.check(self._L.ds_pack_groups(p(self.k32t), p(s.groups["kperm"]), s.nnzb, p(self.kgrp),
-                                              _hip.stream_ptr()), "ds_pack_groups")
+            _hip.launch("ds_pack_groups", p(self.k32t), p(s.groups["kperm"]), s.nnzb, p(self.kgrp))
             if self.m_kind == 1:
                 self.mgrp = self.ms32[s.groups["kperm64"]].contiguous()  # node-scalar mass values in group order
             if self._mfma is not None:
                 if self.kc is None:
                     self.kc = torch.empty((s.nnzb, 3, 4), dtype=torch.bfloat16, device=self.device)
-                _hip.check(self._L.ds_pack_kc(p(self.k32), p(self._mfma["kperm"]), s.nnzb, p(self.kc), _hip.stream_ptr()),
-                           "ds_pack_kc")
+                _hip.launch("ds_pack_kc", p(self.k32), p(self._mfma["kperm"]), s.nnzb, p(self.kc))
             if self.group_jacobi and self._mfma is not None:
                 md = self._mfma_dense
                 if self.tgrp is None:
@@ -220,18 +214,15 @@ class HipModalOps(_HipBlockOps):
                     self.tgrp = torch.empty((ng, 3 * self.group_jacobi, 3 * self.group_jacobi), dtype=torch.float32, device=self.device)
                     self.kc_dense = torch.zeros((md["nblocks"], 3, 4), dtype=torch.bfloat16, device=self.device)
                     self.dinv_id = torch.eye(3, dtype=torch.float32, device=self.device).reshape(1, 9).repeat(s.nv, 1).contiguous()
-                _hip.check(self._L.ds_group_inverse(p(s.rowptr), p(s.colidx), p(self.k32), s.nv, self.group_jacobi, p(self.tgrp),
-                                                    _hip.stream_ptr()), "ds_group_inverse")
+                _hip.launch("ds_group_inverse", p(s.rowptr), p(s.colidx), p(self.k32), s.nv, self.group_jacobi, p(self.tgrp))
                 mt_ = self._mfma
-                _hip.check(self._L.ds_group_pack_kc(p(self.k32), p(self.tgrp), p(mt_["gptr"]), p(mt_["gmeta"]), p(mt_["gbase"]),
-                                                    p(mt_["kperm"]), self.group_jacobi, s.nv, p(self.kc_dense), _hip.stream_ptr()),
-                           "ds_group_pack_kc")
+                _hip.launch("ds_group_pack_kc", p(self.k32), p(self.tgrp), p(mt_["gptr"]), p(mt_["gmeta"]), p(mt_["gbase"]),
+                            p(mt_["kperm"]), self.group_jacobi, s.nv, p(self.kc_dense))
             if self._mfma32 is not None:
                 if self.k4 is None:  # (zeros: the 16 bytes of slack behind the last block are read and must be finite)
                     self.k4 = torch.zeros((s.nnzb * 9 + 4,), dtype=torch.float32, device=self.device)
                     self._kperm4 = self._mfma32["kperm"].long()
-                _hip.check(self._L.ds_pack_groups(p(self.k32), p(self._mfma32["kperm"]), s.nnzb, p(self.k4),
-                                                  _hip.stream_ptr()), "ds_pack_groups")
+                _hip.launch("ds_pack_groups", p(self.k32), p(self._mfma32["kperm"]), s.nnzb, p(self.k4))
                 if self.m_kind == 1:
                     if self.m4 is None:
                         self.m4 = torch.zeros((s.nnzb + 4,), dtype=torch.float32, device=self.device)

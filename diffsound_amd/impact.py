@@ -188,9 +188,7 @@ class ContactSurface:
         P, m = elem.shape[0], U.shape[1]
         out = torch.empty((P, m), dtype=torch.float64, device=self.device) if want_out else None
         vec = torch.empty((P, m, 3), dtype=torch.float64, device=self.device) if want_vec else None
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_mode_sample_fwd(*self._args(U, elem, L, d), _hip.ptr(out), _hip.ptr(vec),
-                                                     _hip.stream_ptr()), "ds_mode_sample_fwd")
+        _hip.launch("ds_mode_sample_fwd", *self._args(U, elem, L, d), _hip.ptr(out), _hip.ptr(vec), device=self.device)
         return out, vec
 
     def _launch_bwd(self, elem, L, d, gout, want_l, want_d):
@@ -201,9 +199,7 @@ class ContactSurface:
                              "U_hat changed between forward and backward")
         gL = torch.empty((P, 4), dtype=torch.float64, device=self.device) if want_l else None
         gdir = torch.empty((P, 3), dtype=torch.float64, device=self.device) if want_d else None
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_mode_sample_bwd(*self._args(U, elem, L, d), _hip.ptr(gout), _hip.ptr(gL),
-                                                     _hip.ptr(gdir), _hip.stream_ptr()), "ds_mode_sample_bwd")
+        _hip.launch("ds_mode_sample_bwd", *self._args(U, elem, L, d), _hip.ptr(gout), _hip.ptr(gL), _hip.ptr(gdir), device=self.device)
         return gL, gdir
 
     # ------------------------------------------------------------------ public interface

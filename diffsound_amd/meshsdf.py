@@ -129,10 +129,8 @@ class MeshDistance:
         self.num_faces = int(f.shape[0])
         f32 = self.faces.int().contiguous()
         self._records = torch.empty((self.num_faces, 16), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(_hip.lib().ds_mesh_sdf_pack(self.vertices.data_ptr(), f32.data_ptr(), self.vertices.shape[0],
-                                                   self.num_faces, self._records.data_ptr(), _hip.stream_ptr()),
-                       "ds_mesh_sdf_pack")
+        _hip.launch("ds_mesh_sdf_pack", self.vertices.data_ptr(), f32.data_ptr(), self.vertices.shape[0], self.num_faces,
+                    self._records.data_ptr(), device=self.device)
 
     def query(self, points, unsigned=False, face=False, winding=False, split=None):
         """All outputs of one pass as a dict: ``signed`` always, ``unsigned`` / ``face`` (int64) / ``winding`` on
@@ -142,7 +140,6 @@ class MeshDistance:
         lead = tuple(p.shape[:-1])
         pts = p.to(self.device, torch.float32).reshape(-1, 3).contiguous()
         P = pts.shape[0]
-        lib = _hip.lib()
         new = lambda dt: torch.empty(P, dtype=dt, device=self.device)
         out_s = new(torch.float32)
         out_u = new(torch.float32) if unsigned else None
@@ -150,15 +147,14 @@ class MeshDistance:
         out_w = new(torch.float32) if winding else None
         work, nbytes = None, 0
         if split is None or split:
-            nbytes = int(lib.ds_mesh_sdf_workspace_bytes(P, self.num_faces, 1 if split else 0))
+            # (not _hip.workspace: a negative answer is this query's refusal, and 0 means no workspace at all)
+            nbytes = int(_hip.lib().ds_mesh_sdf_workspace_bytes(P, self.num_faces, 1 if split else 0))
             if nbytes < 0:
                 raise ValueError(f"MeshDistance: too many points ({P})")
             if nbytes:
                 work = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            _hip.check(lib.ds_mesh_sdf_query(pts.data_ptr(), P, self._records.data_ptr(), self.num_faces, out_s.data_ptr(),
-                                             _hip.ptr(out_u), _hip.ptr(out_f), _hip.ptr(out_w), _hip.ptr(work), nbytes,
-                                             _hip.stream_ptr()), "ds_mesh_sdf_query")
+        _hip.launch("ds_mesh_sdf_query", pts.data_ptr(), P, self._records.data_ptr(), self.num_faces, out_s.data_ptr(), _hip.ptr(out_u),
+                    _hip.ptr(out_f), _hip.ptr(out_w), _hip.ptr(work), nbytes, device=self.device)
         res = {"signed": out_s.reshape(lead)}
         if unsigned:
             res["unsigned"] = out_u.reshape(lead)

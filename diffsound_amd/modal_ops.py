@@ -360,11 +360,9 @@ class TetSystem:
                 # numeric assembly is part of the pass the metric defines).
                 self.assemblies_skipped += 1
                 return
-        L = _hip.lib()
         p = _hip.ptr
-        _hip.check(L.ds_assemble_kml(p(self.vertices), p(self.tets), self.T, self.N, self.nv, p(self.cptr),
-                                     p(self.clist), self.nnzb, p(self.dtab), p(self.mtab), p(self._tetgeo),
-                                     p(self.klam), p(self.kmu), p(self.ms), _hip.stream_ptr()), "ds_assemble_kml")
+        _hip.launch("ds_assemble_kml", p(self.vertices), p(self.tets), self.T, self.N, self.nv, p(self.cptr), p(self.clist), self.nnzb,
+                    p(self.dtab), p(self.mtab), p(self._tetgeo), p(self.klam), p(self.kmu), p(self.ms))
         self._assembled_generation = self.geometry_generation
         if self._coarse is not None:
             # (the corner-node level always receives the coordinates it is to be assembled on when the caller handed any over:
@@ -378,10 +376,9 @@ class TetSystem:
         grad = torch.zeros((self.nv, 3), dtype=torch.float64, device=self.device)
         U = U.contiguous()
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_geometry_grad(p(self.tets), self.T, self.N, self.nv, p(self._tetgeo), p(U), U.stride(0),
-                                               U.shape[1], p(gk.double().contiguous()), p(gm.double().contiguous()),
-                                               float(lam), float(mu), p(gtab), p(gwt), gtab.shape[0], p(self.mtab), p(grad),
-                                               _hip.stream_ptr()), "ds_geometry_grad")
+        _hip.launch("ds_geometry_grad", p(self.tets), self.T, self.N, self.nv, p(self._tetgeo), p(U), U.stride(0), U.shape[1],
+                    p(gk.double().contiguous()), p(gm.double().contiguous()), float(lam), float(mu), p(gtab), p(gwt), gtab.shape[0],
+                    p(self.mtab), p(grad))
         return grad if self.perm is None else grad[self.inv_perm]
 
     def gradient_rule(self):
@@ -417,10 +414,8 @@ class TetSystem:
         work = torch.empty((self.T, 12), dtype=torch.float64, device=dev)
         grad = torch.empty((self.nv, 3), dtype=torch.float64, device=dev)
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_geometry_grad_tangent(p(self.tets), self.T, self.N, self.nv, p(self._tetgeo), p(U), _ld(U), m,
-                                                       p(gk), p(gm), C.ctypes.data, p(gtab), p(gwt), gtab.shape[0],
-                                                       p(self.mtab), p(cptr), p(cinc), p(work), p(grad), _hip.stream_ptr()),
-                   "ds_geometry_grad_tangent")
+        _hip.launch("ds_geometry_grad_tangent", p(self.tets), self.T, self.N, self.nv, p(self._tetgeo), p(U), _ld(U), m, p(gk), p(gm),
+                    C.ctypes.data, p(gtab), p(gwt), gtab.shape[0], p(self.mtab), p(cptr), p(cinc), p(work), p(grad))
         return grad if self.perm is None else grad[self.inv_perm]
 
     # scipy views for tests / interop (host copies, in the caller's node numbering)

@@ -233,11 +233,10 @@ class ModalPipeline:
             raise ValueError("target clip length differs from the oscillator's sample_num")
         a, b, md = res.a_lambda.double().contiguous(), res.b_mu.double().contiguous(), res.m_diag.double().contiguous()
         p = _hip.ptr
-        _hip.check(_hip.lib().ds_readout_pass(p(ev.double().contiguous()), p(a), p(b), p(md), m, lam, mu, dlam_dE, dlam_dnu,
-                                              dmu_dE, dmu_dnu, float(osc.alpha), float(osc.beta), p(osc._force),
-                                              int(osc._force.shape[1]), S, float(osc.sr), p(tgt), 1 if backward else 0,
-                                              p(audio), p(freqs), p(work), p(fwork), p(out), _hip.stream_ptr()),
-                   "ds_readout_pass")
+        # (no device guard: the lane runs with its device set, as for the operator layer's launches)
+        _hip.launch("ds_readout_pass", p(ev.double().contiguous()), p(a), p(b), p(md), m, lam, mu, dlam_dE, dlam_dnu, dmu_dE, dmu_dnu,
+                    float(osc.alpha), float(osc.beta), p(osc._force), int(osc._force.shape[1]), S, float(osc.sr), p(tgt),
+                    1 if backward else 0, p(audio), p(freqs), p(work), p(fwork), p(out))
         host = out.tolist()  # the pass's one synchronisation
         # what code written against the reference reads off the bank after a forward (oscillator.py:303-305; e.g.
         # experiments/material_sync_train.py:167): the undamped and damped frequencies of this pass

@@ -1,7 +1,9 @@
 """What the kernel tests share (not a test module).  Guard zones for kernel outputs: an output placed PAD elements inside a
 NaN-filled device buffer, so that a write before its start or past its end, or an element left unwritten, is seen after the
-call.  And the small helpers: the library handle, uploads, case ids and the printed error / bound ratio."""
+call.  And the small helpers: the library handle, uploads, case ids, the printed error / bound ratio and the comparisons of
+two guarded outputs."""
 import numpy as np
+import pytest
 import torch
 
 PAD = 64
@@ -35,6 +37,33 @@ def _ratio(tag, case, got, ref, bound):
     worst = float(r.max())
     print(f"RATIO {tag} {_id(case)} {worst:.4g}" if case is not None else f"RATIO {tag} {worst:.4g}")
     return worst
+
+
+def same_bits(a, b):
+    """Two Guarded outputs hold the same bytes, guard zones included."""
+    return np.array_equal(a.buf.cpu().numpy().view(np.uint8), b.buf.cpu().numpy().view(np.uint8))
+
+
+def outside_untouched(g, what):
+    """The guard zones of the Guarded ``g`` are still NaN, whatever the output itself holds."""
+    whole = g.buf.cpu().numpy()
+    assert np.isnan(whole[:PAD]).all() and np.isnan(whole[PAD + g.n:]).all(), f"{what}: written outside"
+
+
+def same_on_other_device(run):
+    """``run(device)`` builds its operands on ``device`` and returns a tuple of results.  Made with device 0 current and the
+    operands on device 1, it gives what it gives with device 1 current, bit for bit, on device 1.  Skips on one device."""
+    n = torch.cuda.device_count()
+    if n < 2:
+        pytest.skip(f"needs two HIP devices, {n} visible")
+    other = torch.device("cuda:1")
+    with torch.cuda.device(1):
+        want = run(other)
+    with torch.cuda.device(0):
+        got = run(other)
+    assert len(got) == len(want) > 0
+    for g, w in zip(got, want):
+        assert g.device == other and g.dtype == w.dtype and g.cpu().numpy().tobytes() == w.cpu().numpy().tobytes()
 
 
 class Guarded:

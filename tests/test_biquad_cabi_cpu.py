@@ -2,35 +2,21 @@
 and refuse bad arguments before any device work, the earlier reason first."""
 import os
 import re
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _cabi import assert_refused, hip_built as _hip_built, refusal_calls, symbols_declared  # noqa: E402
+
 NAMES = ("ds_biquad_workspace_bytes", "ds_biquad_fwd", "ds_biquad_bwd")
 
 
-def _hip_built():
-    from diffsound_amd import _hip
-
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as g
-
-        g.build()
-    return _hip
-
-
 def test_biquad_symbols():
+    header, src = symbols_declared(NAMES, "biquad.hip")
     _hip = _hip_built()
-    lib = _hip.lib()
-    header = open(os.path.join(ROOT, "include", "diffsound_hip.h")).read()
-    for name in NAMES:
-        assert name in _hip.EXPORTED_SYMBOLS and name in _hip._SIGNATURES and hasattr(lib, name)
-        assert re.search(r"\b%s\s*\(" % name, header)
     assert re.search(r"#define DS_BIQUAD_MAX_SECTIONS 16\b", header) and re.search(r"#define DS_BIQUAD_MAX_ROWS 65535\b", header)
-    assert lib.ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
-    csrc = os.path.join(ROOT, "diffsound_amd", "csrc")
-    assert re.search(r"\bbiquad\.hip\b", open(os.path.join(csrc, "Makefile")).read())
-    src = open(os.path.join(csrc, "biquad.hip")).read()
+    assert _hip.lib().ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
     assert "atomic" not in src
     assert "osc_scan::RUN" in src and not re.search(r"constexpr\s+int\s+RUN\b", src)   # the scan's constant, no second one
     # the two promises are said where the caller reads them, and the workspace formula with them
@@ -55,29 +41,19 @@ BAD_BWD = [(dict(gy=None), "null pointer"), (dict(work=None), "null pointer"), (
            (dict(gsos=None), "null pointer"), (dict(gy=OK + 2), "misaligned operand"), (dict(gx=OK + 2), "misaligned operand"),
            (dict(gsos=OK + 4), "misaligned operand"), (dict(work=OK + 8), "work not 16-byte aligned"),
            (dict(bytes=8 * 2 * 7 * 3 - 1), "bytes, 336 needed")]
-CALLS = [("ds_biquad_fwd", FWD, c, t) for c, t in BAD + BAD_FWD] + [("ds_biquad_bwd", BWD, c, t) for c, t in BAD + BAD_BWD]
 # the order of the refusals: the earlier reason wins where two are wrong
 ORDER = [(dict(x=None, B=0), "null pointer"), (dict(B=0, S=17), "empty problem"), (dict(B=65536, S=17), "above 65535"),
          (dict(S=17, per_clip=2), "sections above 16"), (dict(per_clip=2, x=OK + 2), "neither 0 nor 1")]
 ORDER_BWD = [(dict(per_clip=2, work=OK + 8), "neither 0 nor 1"), (dict(gx=OK + 2, work=OK + 8), "misaligned operand"),
              (dict(gsos=OK + 4, bytes=1), "misaligned operand"), (dict(work=OK + 8, bytes=1), "work not 16-byte aligned")]
-ORDERED = ([(fn, order, c, t) for fn, order in (("ds_biquad_fwd", FWD), ("ds_biquad_bwd", BWD)) for c, t in ORDER] +
-           [("ds_biquad_bwd", BWD, c, t) for c, t in ORDER_BWD])
+CALLS, IDS = refusal_calls(("ds_biquad_fwd", FWD), ("ds_biquad_bwd", BWD), BAD, BAD_FWD, BAD_BWD, ORDER, ORDER_BWD)
 
 
-def _ids(calls):
-    return [f"{f[3:]}-" + ",".join(f"{k}={v}" for k, v in c.items()) for f, _, c, _ in calls]
-
-
-@pytest.mark.parametrize("fn,order,change,text", CALLS + ORDERED, ids=_ids(CALLS + ORDERED))
+@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=IDS)
 def test_biquad_arguments_are_checked_first(fn, order, change, text):
     """Every host-side refusal: a non-zero status and a message that names the entry point and the reason, in front of any
-    launch (the pointers are fakes that a launch would fault on; the call needs no device)."""
-    lib = _hip_built().lib()
-    args = [dict(GOOD, **change)[k] for k in order]
-    assert getattr(lib, fn)(*args, None) != 0
-    msg = lib.ds_last_error().decode()
-    assert fn in msg and text in msg, msg
+    launch."""
+    assert_refused(fn, order, GOOD, change, text)
 
 
 def test_biquad_workspace_query_needs_no_device():

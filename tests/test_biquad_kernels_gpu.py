@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _biquad_ref as BQ  # noqa: E402
-from _guarded import Guarded, _lib, _ratio, _up  # noqa: E402
+from _guarded import Guarded, _lib, _ratio, _up, same_bits as _same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -45,10 +45,6 @@ def _run(case):
     inputs = BQ.inputs(case)
     f = BQ.forward(inputs[0], inputs[1])
     return inputs, f, _call(case, inputs), _call(case, inputs)
-
-
-def _same_bits(a, b):
-    return np.array_equal(a.buf.cpu().numpy().view(np.uint8), b.buf.cpu().numpy().view(np.uint8))
 
 
 @pytest.mark.parametrize("case", BQ.CASES, ids=IDS)

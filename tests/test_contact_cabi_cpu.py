@@ -2,35 +2,21 @@
 Makefile, and refuse bad arguments before any device work."""
 import os
 import re
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _cabi import assert_refused, hip_built as _hip_built, refusal_calls, symbols_declared  # noqa: E402
+
 NAMES = ("ds_contact_workspace_bytes", "ds_contact_fwd", "ds_contact_bwd")
 
 
-def _hip_built():
-    from diffsound_amd import _hip
-
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as g
-
-        g.build()
-    return _hip
-
-
 def test_contact_symbols():
+    header, src = symbols_declared(NAMES, "contact.hip")
     _hip = _hip_built()
-    lib = _hip.lib()
-    header = open(os.path.join(ROOT, "include", "diffsound_hip.h")).read()
-    for name in NAMES:
-        assert name in _hip.EXPORTED_SYMBOLS and hasattr(lib, name)
-        assert re.search(r"\b%s\s*\(" % name, header)
     assert re.search(r"#define DS_CONTACT_MAX_MODES 512\b", header)
-    assert lib.ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
-    csrc = os.path.join(ROOT, "diffsound_amd", "csrc")
-    assert re.search(r"\bcontact\.hip\b", open(os.path.join(csrc, "Makefile")).read())
-    src = open(os.path.join(csrc, "contact.hip")).read()
+    assert _hip.lib().ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
     assert "__shared__" not in src and "__syncthreads" not in src
     assert "atomic" not in src.replace("no atomics", "")
 
@@ -58,22 +44,13 @@ BAD_BWD = [(dict(gforce=None), "null pointer"), (dict(work=None), "null pointer"
            (dict(gd=None), "gd and gw go together"), (dict(gw=None), "gd and gw go together"),
            (dict(gvel=None), "go together"), (dict(gmass=None, gstiff=None), "go together"),
            (dict(gforce=OK + 2), "misaligned operand"), (dict(ggain=OK + 4), "misaligned operand")]
-CALLS = [("ds_contact_fwd", FWD, c, t) for c, t in BAD + BAD_FWD] + [("ds_contact_bwd", BWD, c, t) for c, t in BAD + BAD_BWD]
+CALLS, IDS = refusal_calls(("ds_contact_fwd", FWD), ("ds_contact_bwd", BWD), BAD, BAD_FWD, BAD_BWD, id_from=11, id_sep="-")
 
 
-def _cid(f, c):
-    return f[11:] + "-" + "-".join(f"{k}={v}" for k, v in c.items())
-
-
-@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=[_cid(f, c) for f, _, c, _ in CALLS])
+@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=IDS)
 def test_contact_arguments_are_checked_first(fn, order, change, text):
-    """Every host-side refusal: DS_ERR_ARG and a message that names the entry point and the reason, in front of any launch
-    (the pointers are fakes that a launch would fault on; the call needs no device)."""
-    lib = _hip_built().lib()
-    args = [dict(GOOD, **change)[k] for k in order]
-    assert getattr(lib, fn)(*args, None) == 1  # DS_ERR_ARG
-    msg = lib.ds_last_error().decode()
-    assert fn in msg and text in msg, msg
+    """Every host-side refusal: DS_ERR_ARG and a message that names the entry point and the reason, in front of any launch."""
+    assert_refused(fn, order, GOOD, change, text, status=1)
 
 
 def test_contact_workspace_query_needs_no_device():

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _contact_ref as C  # noqa: E402
-from _guarded import Guarded, _lib, _ratio, _up  # noqa: E402
+from _guarded import Guarded, _lib, _ratio, _up, same_bits as _same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -63,10 +63,6 @@ def _refs(i):
         adj = C.adjoint(g, d, w, c, M, v0, kH, p, R, dtype=dt)
         out.append(dict(adj, force=fw["force"], f=fw["f"]))
     return out
-
-
-def _same_bits(a, b):
-    return np.array_equal(a.buf.cpu().numpy().view(np.uint8), b.buf.cpu().numpy().view(np.uint8))
 
 
 @pytest.mark.parametrize("i", range(len(C.CASES)), ids=IDS)

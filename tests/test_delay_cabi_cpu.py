@@ -2,36 +2,22 @@
 Makefile, and refuse bad arguments before any device work."""
 import os
 import re
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _cabi import assert_refused, hip_built as _hip_built, refusal_calls, symbols_declared  # noqa: E402
+
 NAMES = ("ds_delay_workspace_bytes", "ds_delay_fwd", "ds_delay_bwd")
 
 
-def _hip_built():
-    from diffsound_amd import _hip
-
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as g
-
-        g.build()
-    return _hip
-
-
 def test_delay_symbols():
+    header, src = symbols_declared(NAMES, "delay.hip")
     _hip = _hip_built()
-    lib = _hip.lib()
-    header = open(os.path.join(ROOT, "include", "diffsound_hip.h")).read()
-    for name in NAMES:
-        assert name in _hip.EXPORTED_SYMBOLS and name in _hip._SIGNATURES and hasattr(lib, name)
-        assert re.search(r"\b%s\s*\(" % name, header)
     assert re.search(r"#define DS_DELAY_HALF_TAPS 8\b", header) and re.search(r"#define DS_DELAY_MAX_SLOPE 0\.5\b", header)
     assert re.search(r"#define DS_DELAY_MAX_ROWS 65535\b", header)
-    assert lib.ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
-    csrc = os.path.join(ROOT, "diffsound_amd", "csrc")
-    assert re.search(r"\bdelay\.hip\b", open(os.path.join(csrc, "Makefile")).read())
-    src = open(os.path.join(csrc, "delay.hip")).read()
+    assert _hip.lib().ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
     assert "atomic" not in src.replace("No atomics", "").replace("no atomics", "")
     # what the header promises for every tau is said where the caller reads it
     for text in ("before any conversion to", "outside [-R, S + R) yields y = 0", "non-finite tau(t) yields y = NaN", "stays inside [0, S)"):
@@ -51,29 +37,19 @@ BAD_FWD = [(dict(y=None), "null pointer"), (dict(y=OK + 2), "misaligned operand"
 BAD_BWD = [(dict(gy=None), "null pointer"), (dict(work=None), "null pointer"),
            (dict(bytes=8 * 2 * 7 - 1), "bytes, 112 needed"), (dict(work=OK + 8), "work not 16-byte aligned"),
            (dict(gy=OK + 2), "misaligned operand"), (dict(gs=OK + 2), "misaligned operand"), (dict(gtau=OK + 4), "misaligned operand")]
-CALLS = [("ds_delay_fwd", FWD, c, t) for c, t in BAD + BAD_FWD] + [("ds_delay_bwd", BWD, c, t) for c, t in BAD + BAD_BWD]
 # the order of the refusals: the earlier reason wins where two are wrong
 ORDER = [(dict(s=None, B=0), "null pointer"), (dict(B=0, hop=0), "empty problem"), (dict(B=65536, hop=0), "above 65535"),
          (dict(hop=0, s=OK + 2), "is not positive")]
 ORDER_BWD = [(dict(hop=0, bytes=1), "is not positive"), (dict(bytes=1, work=OK + 8), "112 needed"),
              (dict(work=OK + 8, gs=OK + 2), "work not 16-byte aligned")]
-ORDERED = ([(fn, order, c, t) for fn, order in (("ds_delay_fwd", FWD), ("ds_delay_bwd", BWD)) for c, t in ORDER] +
-           [("ds_delay_bwd", BWD, c, t) for c, t in ORDER_BWD])
+CALLS, IDS = refusal_calls(("ds_delay_fwd", FWD), ("ds_delay_bwd", BWD), BAD, BAD_FWD, BAD_BWD, ORDER, ORDER_BWD)
 
 
-def _ids(calls):
-    return [f"{f[3:]}-" + ",".join(f"{k}={v}" for k, v in c.items()) for f, _, c, _ in calls]
-
-
-@pytest.mark.parametrize("fn,order,change,text", CALLS + ORDERED, ids=_ids(CALLS + ORDERED))
+@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=IDS)
 def test_delay_arguments_are_checked_first(fn, order, change, text):
     """Every host-side refusal: a non-zero status and a message that names the entry point and the reason, in front of any
-    launch (the pointers are fakes that a launch would fault on; the call needs no device)."""
-    lib = _hip_built().lib()
-    args = [dict(GOOD, **change)[k] for k in order]
-    assert getattr(lib, fn)(*args, None) != 0
-    msg = lib.ds_last_error().decode()
-    assert fn in msg and text in msg, msg
+    launch."""
+    assert_refused(fn, order, GOOD, change, text)
 
 
 def test_delay_workspace_query_needs_no_device():

@@ -14,7 +14,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _delay_ref as DL  # noqa: E402
-from _guarded import Guarded, _lib, _ratio, _up  # noqa: E402
+from _guarded import Guarded, _lib, _ratio, _up, same_bits as _same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -45,10 +45,6 @@ def _call(case, inputs, with_gs=True, with_gtau=True):
 def _run(case):
     inputs = DL.inputs(case)
     return inputs, _call(case, inputs), _call(case, inputs)
-
-
-def _same_bits(a, b):
-    return np.array_equal(a.buf.cpu().numpy().view(np.uint8), b.buf.cpu().numpy().view(np.uint8))
 
 
 @pytest.mark.parametrize("case", DL.CASES, ids=IDS)

@@ -9,32 +9,16 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _fir_ref as F  # noqa: E402
+from _cabi import assert_refused, hip_built as _hip_built, refusal_calls, symbols_declared  # noqa: E402
 
 NAMES = ("ds_fir_workspace_bytes", "ds_fir_fwd", "ds_fir_bwd")
 
 
-def _hip_built():
-    from diffsound_amd import _hip
-
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as g
-
-        g.build()
-    return _hip
-
-
 def test_fir_symbols():
+    header, src = symbols_declared(NAMES, "fir.hip")
     _hip = _hip_built()
-    lib = _hip.lib()
-    header = open(os.path.join(ROOT, "include", "diffsound_hip.h")).read()
-    for name in NAMES:
-        assert name in _hip.EXPORTED_SYMBOLS and name in _hip._SIGNATURES and hasattr(lib, name)
-        assert re.search(r"\b%s\s*\(" % name, header)
     assert re.search(r"#define DS_FIR_MAX_TAPS 65536\b", header) and re.search(r"#define DS_FIR_MAX_ROWS 65535\b", header)
-    assert lib.ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
-    csrc = os.path.join(ROOT, "diffsound_amd", "csrc")
-    assert re.search(r"\bfir\.hip\b", open(os.path.join(csrc, "Makefile")).read())
-    src = open(os.path.join(csrc, "fir.hip")).read()
+    assert _hip.lib().ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
     assert "atomic" not in src
     assert len(re.findall(r"\bacc\[i\] \+= av \* ", src)) == 1   # one inner loop for the three sums, not three copies
     # the promises are said where the caller reads them, and the workspace formula with them
@@ -72,29 +56,18 @@ BAD_BWD = [(dict(gy=None), "null pointer"), (dict(work=None), "null pointer"), (
            (dict(gx=None, gh=None), "gx and gh are both NULL"), (dict(gx=None, gh=None, work=None), "gx and gh are both NULL"),
            (dict(work=OK + 8), "work not 16-byte aligned"), (dict(bytes=NEED - 1), f"bytes, {NEED} needed"),
            (dict(gx=None, bytes=0), f"bytes, {NEED} needed")]
-CALLS = [("ds_fir_fwd", FWD, c, t) for c, t in BAD + BAD_FWD] + [("ds_fir_bwd", BWD, c, t) for c, t in BAD + BAD_BWD]
 # the order of the refusals: the earlier reason wins where two are wrong
 ORDER = [(dict(x=None, B=0), "null pointer"), (dict(N=0, B=65536), "empty problem"), (dict(B=65536, L=65537), "above 65535"),
          (dict(L=65537, H=4), "taps above 65536"), (dict(H=4, x=OK + 2), "not a multiple")]
 ORDER_BWD = [(dict(gy=OK + 2, gx=None, gh=None), "misaligned operand"), (dict(gx=None, gh=None, bytes=0), "both NULL"),
              (dict(work=OK + 8, bytes=1), "work not 16-byte aligned"), (dict(H=4, work=OK + 8), "not a multiple")]
-ORDERED = ([(fn, order, c, t) for fn, order in (("ds_fir_fwd", FWD), ("ds_fir_bwd", BWD)) for c, t in ORDER] +
-           [("ds_fir_bwd", BWD, c, t) for c, t in ORDER_BWD])
+CALLS, IDS = refusal_calls(("ds_fir_fwd", FWD), ("ds_fir_bwd", BWD), BAD, BAD_FWD, BAD_BWD, ORDER, ORDER_BWD)
 
 
-def _ids(calls):
-    return [f"{f[3:]}-" + ",".join(f"{k}={v}" for k, v in c.items()) for f, _, c, _ in calls]
-
-
-@pytest.mark.parametrize("fn,order,change,text", CALLS + ORDERED, ids=_ids(CALLS + ORDERED))
+@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=IDS)
 def test_fir_arguments_are_checked_first(fn, order, change, text):
-    """Every host-side refusal: a non-zero status and a message that names the entry point and the reason, in front of any
-    launch (the pointers are fakes that a launch would fault on; the call needs no device)."""
-    lib = _hip_built().lib()
-    args = [dict(GOOD, **change)[k] for k in order]
-    assert getattr(lib, fn)(*args, None) == 1   # DS_ERR_ARG
-    msg = lib.ds_last_error().decode()
-    assert fn in msg and text in msg, msg
+    """Every host-side refusal: DS_ERR_ARG and a message that names the entry point and the reason, in front of any launch."""
+    assert_refused(fn, order, GOOD, change, text, status=1)
 
 
 def test_fir_workspace_query_needs_no_device():

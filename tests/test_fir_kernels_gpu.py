@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _fir_ref as F  # noqa: E402
-from _guarded import Guarded, _lib, _ratio, _up  # noqa: E402
+from _guarded import Guarded, _lib, _ratio, _up, outside_untouched as _outside_untouched, same_bits as _same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -51,15 +51,6 @@ def _call(case, inputs, want=("y", "gx", "gh")):
 def _run(case):
     inputs, f, b = F.reference(case)
     return inputs, f, b, _call(case, inputs), _call(case, inputs)
-
-
-def _same_bits(a, b):
-    return np.array_equal(a.buf.cpu().numpy().view(np.uint8), b.buf.cpu().numpy().view(np.uint8))
-
-
-def _outside_untouched(g, what):
-    whole = g.buf.cpu().numpy()
-    assert np.isnan(whole[:64]).all() and np.isnan(whole[64 + g.n:]).all(), f"{what}: written outside"
 
 
 @pytest.mark.parametrize("case", F.CASES, ids=IDS)

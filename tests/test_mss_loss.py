@@ -12,11 +12,14 @@ device (kernels); the Spectrogram underneath stays a restated third-party algori
 The kernels on their own - element by element through the C ABI, at hops, clip lengths and frame counts this file never uses - are
 tests/test_stft_kernels_gpu.py (GPU) and tests/test_stft_ref_cpu.py (its references and bounds, no GPU)."""
 import os
+import sys
+
 import numpy as np
 import pytest
 import torch
 
-from oracle import mss_loss as omss
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from oracle import mss_loss as omss  # noqa: E402
 
 N_FFTS = [2048, 1024, 512, 256, 128, 64]  # the scales of the reference experiments (material_sync_train.py:123-125)
 REAL_FFTS = [512, 256, 128, 64, 32]       # material_real_train.py:110
@@ -251,3 +254,18 @@ def test_geomloss_variant_delegates_at_call_time(dev, monkeypatch):
     assert torch.allclose(one, 2.0 * want_log + want_lin)
     loss.backward()
     assert freq.grad is not None and float(freq.grad.abs().sum()) > 0
+
+
+@pytest.mark.gpu
+def test_loss_runs_on_its_operands_device():
+    """One scale at the smallest transform the kernels take (n_fft = 8, hop 2, 5 samples), forward and backward, with the
+    clips off the current device."""
+    from _guarded import same_on_other_device
+    from diffsound_amd.ddsp.mss_loss import MSSLoss
+
+    def run(device):
+        x = torch.tensor([[0.5, -0.25, 1.0, 0.125, -0.75]], device=device, requires_grad=True)
+        loss = MSSLoss([8], 32000, type="l1_loss")(x, torch.tensor([[0.25, 0.5, -1.0, 0.0, 0.375]], device=device))
+        return loss.detach(), torch.autograd.grad(loss, x)[0]
+
+    same_on_other_device(run)

@@ -2,36 +2,22 @@
 Makefile, and refuse bad arguments before any device work; so does the Python layer."""
 import os
 import re
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _cabi import assert_refused, hip_built as _hip_built, refusal_calls, symbols_declared  # noqa: E402
+
 NAMES = ("ds_multipole_workspace_bytes", "ds_multipole_fwd", "ds_multipole_bwd")
 
 
-def _hip_built():
-    from diffsound_amd import _hip
-
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as g
-
-        g.build()
-    return _hip
-
-
 def test_multipole_symbols():
+    header, src = symbols_declared(NAMES, "multipole.hip")
     _hip = _hip_built()
-    lib = _hip.lib()
-    header = open(os.path.join(ROOT, "include", "diffsound_hip.h")).read()
-    for name in NAMES:
-        assert name in _hip.EXPORTED_SYMBOLS and hasattr(lib, name)
-        assert re.search(r"\b%s\s*\(" % name, header)
     assert re.search(r"#define DS_MULTIPOLE_MAX_ORDER 32\b", header)
     assert re.search(r"#define DS_MULTIPOLE_MAX_MODES 512\b", header)
-    assert lib.ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
-    csrc = os.path.join(ROOT, "diffsound_amd", "csrc")
-    assert re.search(r"\bmultipole\.hip\b", open(os.path.join(csrc, "Makefile")).read())
-    src = open(os.path.join(csrc, "multipole.hip")).read()
+    assert _hip.lib().ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
     assert "atomic" not in src.replace("No atomics", "")
     assert "#pragma clang fp contract(off)" in src
 
@@ -54,22 +40,13 @@ BAD_BWD = [(dict(gout=None), "null pointer"), (dict(gout=OK + 8), "misaligned op
            (dict(work=None), "null pointer"), (dict(bytes=NEED - 1), "bytes, %d needed" % NEED), (dict(bytes=0), "needed"),
            (dict(work=OK + 8), "work not 16-byte aligned"),
            (dict(gpts=OK + 4), "misaligned operand"), (dict(gcoef=OK + 8), "misaligned operand")]
-CALLS = [("ds_multipole_fwd", FWD, c, t) for c, t in BAD + BAD_FWD] + [("ds_multipole_bwd", BWD, c, t) for c, t in BAD + BAD_BWD]
+CALLS, IDS = refusal_calls(("ds_multipole_fwd", FWD), ("ds_multipole_bwd", BWD), BAD, BAD_FWD, BAD_BWD, id_from=13, id_sep="-")
 
 
-def _cid(f, c):
-    return f[13:] + "-" + "-".join(f"{k}={v}" for k, v in c.items())
-
-
-@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=[_cid(f, c) for f, _, c, _ in CALLS])
+@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=IDS)
 def test_multipole_arguments_are_checked_first(fn, order, change, text):
-    """Every host-side refusal: DS_ERR_ARG and a message that names the entry point and the reason, in front of any launch
-    (the pointers are fakes that a launch would fault on; the call needs no device)."""
-    lib = _hip_built().lib()
-    args = [dict(GOOD, **change)[k] for k in order]
-    assert getattr(lib, fn)(*args, None) == 1  # DS_ERR_ARG
-    msg = lib.ds_last_error().decode()
-    assert fn in msg and text in msg, msg
+    """Every host-side refusal: DS_ERR_ARG and a message that names the entry point and the reason, in front of any launch."""
+    assert_refused(fn, order, GOOD, change, text, status=1)
 
 
 def test_multipole_workspace_query_needs_no_device():

@@ -11,7 +11,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _osc_driven_ref as D  # noqa: E402
 import _osc_ref as R  # noqa: E402
-from _guarded import _ratio, _up, dev as _dev  # noqa: E402
+from _guarded import _ratio, _up, dev as _dev, same_on_other_device  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -146,3 +146,24 @@ def test_time_varying_render_refuses_a_long_force():
     with pytest.raises(ValueError, match="512.*closed-form"):
         osc(non_linear_rate=0.05)
     assert osc.cuda()().shape == (1, 64)  # the closed-form render takes it
+
+
+def _tiny_bank(entry, F):
+    """``run(device)`` of ``entry`` at A = 1, m = 2, S = 64: forward and backward, every launch of the call."""
+    def run(device):
+        leaf = lambda x, dt: torch.tensor(x, dtype=dt, device=device).requires_grad_(True)
+        d, w = leaf([3.0, 5.0], torch.float64), leaf([2 * np.pi * 440.0, 2 * np.pi * 1500.0], torch.float64)
+        amp, force = leaf([[1.0, 0.5]], torch.float32), torch.linspace(1.0, 0.1, F, device=device).reshape(1, F)
+        force.requires_grad_(entry.__name__ == "oscillator_bank_driven")
+        y = entry(d, w, amp, force, 64, SR)
+        weight = torch.linspace(-1.0, 1.0, 64, device=device)
+        return (y.detach(),) + torch.autograd.grad((y * weight).sum(), [t for t in (d, w, amp, force) if t.requires_grad])
+    return run
+
+
+def test_banks_run_on_their_operands_device():
+    """The FIR bank (F = 1) and the driven bank (F = S = 64) with operands off the current device."""
+    from diffsound_amd.ddsp.oscillator import oscillator_bank, oscillator_bank_driven
+
+    same_on_other_device(_tiny_bank(oscillator_bank, 1))
+    same_on_other_device(_tiny_bank(oscillator_bank_driven, 64))

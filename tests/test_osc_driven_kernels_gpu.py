@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _osc_driven_ref as D  # noqa: E402
-from _guarded import Guarded, _lib, _ratio, _up, dev as _dev  # noqa: E402
+from _guarded import Guarded, _lib, _ratio, _up, dev as _dev, same_bits as _same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -49,10 +49,6 @@ def _call(case, inputs):
 def _run(case):
     inputs = D.inputs(case)
     return inputs, _call(case, inputs), _call(case, inputs)
-
-
-def _same_bits(a, b):
-    return np.array_equal(a.buf.cpu().numpy().view(np.uint8), b.buf.cpu().numpy().view(np.uint8))
 
 
 @pytest.mark.parametrize("case", D.CASES, ids=IDS)

@@ -2,35 +2,22 @@
 Makefile, and refuse bad arguments before any device work."""
 import os
 import re
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _cabi import CSRC, assert_refused, hip_built as _hip_built, refusal_calls, symbols_declared  # noqa: E402
+
 NAMES = ("ds_osc_listen_workspace_bytes", "ds_osc_listen_fwd", "ds_osc_listen_bwd")
 
 
-def _hip_built():
-    from diffsound_amd import _hip
-
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as g
-
-        g.build()
-    return _hip
-
-
 def test_osc_listen_symbols():
+    header, listen = symbols_declared(NAMES, "osc_listen.hip")
     _hip = _hip_built()
-    lib = _hip.lib()
-    header = open(os.path.join(ROOT, "include", "diffsound_hip.h")).read()
-    for name in NAMES:
-        assert name in _hip.EXPORTED_SYMBOLS and name in _hip._SIGNATURES and hasattr(lib, name)
-        assert re.search(r"\b%s\s*\(" % name, header)
     assert re.search(r"#define DS_OSC_LISTEN_MAX_CHANNELS 16\b", header)
-    assert lib.ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
-    csrc = os.path.join(ROOT, "diffsound_amd", "csrc")
-    assert re.search(r"\bosc_listen\.hip\b", open(os.path.join(csrc, "Makefile")).read())
-    listen, slide, scan = (open(os.path.join(csrc, n)).read() for n in ("osc_listen.hip", "osc_slide.hip", "osc_scan.h"))
+    assert _hip.lib().ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
+    slide, scan = (open(os.path.join(CSRC, n)).read() for n in ("osc_slide.hip", "osc_scan.h"))
     assert '#include "osc_scan.h"' in listen
     for helper in ("struct lane_gain", "lane_gain load_gain(", "struct lane_cgain", "lane_cgain load_cgain(",
                    "cplx run_from_zero(const double* vr, const double* vi, cplx z1)", "void join_waves(", "double frame_scan(",
@@ -63,29 +50,18 @@ BAD_BWD = [(dict(gy=None), "null pointer"), (dict(gd=None), "null pointer"), (di
            (dict(gd=OK + 4), "gd or gw not 8-byte aligned"), (dict(gw=OK + 4), "gd or gw not 8-byte aligned"),
            (dict(gy=OK + 2), "misaligned operand"), (dict(gamp=OK + 2), "misaligned operand"),
            (dict(gforce=OK + 2), "misaligned operand"), (dict(gh=OK + 4), "misaligned operand")]
-CALLS = [("ds_osc_listen_fwd", FWD, c, t) for c, t in BAD + BAD_FWD] + [("ds_osc_listen_bwd", BWD, c, t) for c, t in BAD + BAD_BWD]
 # the order of the refusals: the earlier reason wins where two are wrong
 ORDER = [(dict(d=None, A=0), "null pointer"), (dict(A=0, C=17), "empty problem"), (dict(A=65536, C=17), "above 65535"),
          (dict(C=17, hop=24), "above 16 channels"), (dict(hop=24, sr=0.0), "not a positive multiple"), (dict(sr=0.0, bytes=1), "sr = 0"),
          (dict(bytes=1, work=OK + 8), "192 needed"), (dict(work=OK + 8, d=OK + 4), "work not 16-byte aligned")]
+CALLS, IDS = refusal_calls(("ds_osc_listen_fwd", FWD), ("ds_osc_listen_bwd", BWD), BAD, BAD_FWD, BAD_BWD, ORDER, id_from=7)
 
 
-def _ids(calls):
-    return [f"{f[7:]}-" + ",".join(f"{k}={v}" for k, v in c.items()) for f, _, c, _ in calls]
-
-
-ORDERED = [(fn, order, c, t) for fn, order in (("ds_osc_listen_fwd", FWD), ("ds_osc_listen_bwd", BWD)) for c, t in ORDER]
-
-
-@pytest.mark.parametrize("fn,order,change,text", CALLS + ORDERED, ids=_ids(CALLS + ORDERED))
+@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=IDS)
 def test_osc_listen_arguments_are_checked_first(fn, order, change, text):
     """Every host-side refusal: a non-zero status and a message that names the entry point and the reason, in front of any
-    launch (the pointers are fakes that a launch would fault on; the call needs no device)."""
-    lib = _hip_built().lib()
-    args = [dict(GOOD, **change)[k] for k in order]
-    assert getattr(lib, fn)(*args, None) != 0
-    msg = lib.ds_last_error().decode()
-    assert fn in msg and text in msg, msg
+    launch."""
+    assert_refused(fn, order, GOOD, change, text)
 
 
 def test_osc_listen_workspace_query_needs_no_device():

@@ -15,7 +15,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import _osc_listen_ref as LS  # noqa: E402
-from _guarded import Guarded, _lib, _ratio, _up  # noqa: E402
+from _guarded import Guarded, _lib, _ratio, _up, same_bits as _same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -57,10 +57,6 @@ def _run(case):
 def _ref_backward(case):
     d, w, amp, force, h, gy = LS.inputs(case)
     return LS.backward(gy, d, w, amp, force, h, case[6])
-
-
-def _same_bits(a, b):
-    return np.array_equal(a.buf.cpu().numpy().view(np.uint8), b.buf.cpu().numpy().view(np.uint8))
 
 
 @pytest.mark.parametrize("case", LS.CASES, ids=IDS)

@@ -2,42 +2,29 @@
 Makefile, and refuse bad arguments before any device work."""
 import os
 import re
+import sys
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _cabi import CSRC, assert_refused, hip_built as _hip_built, refusal_calls, symbols_declared  # noqa: E402
+
 NAMES = ("ds_osc_slide_workspace_bytes", "ds_osc_slide_fwd", "ds_osc_slide_bwd")
 
 
-def _hip_built():
-    from diffsound_amd import _hip
-
-    if not os.path.exists(_hip.LIB_PATH):
-        import __graft_entry__ as g
-
-        g.build()
-    return _hip
-
-
 def test_osc_slide_symbols():
+    header, slide = symbols_declared(NAMES, "osc_slide.hip")
     _hip = _hip_built()
-    lib = _hip.lib()
-    header = open(os.path.join(ROOT, "include", "diffsound_hip.h")).read()
-    for name in NAMES:
-        assert name in _hip.EXPORTED_SYMBOLS and hasattr(lib, name)
-        assert re.search(r"\b%s\s*\(" % name, header)
     assert re.search(r"#define DS_OSC_SCAN_RUN 16\b", header)
-    assert lib.ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
-    csrc = os.path.join(ROOT, "diffsound_amd", "csrc")
-    assert re.search(r"\bosc_slide\.hip\b", open(os.path.join(csrc, "Makefile")).read())
-    slide, driven, scan = (open(os.path.join(csrc, n)).read() for n in ("osc_slide.hip", "osc_driven.hip", "osc_scan.h"))
+    assert _hip.lib().ds_abi_version() == 45 == _hip.ABI_VERSION  # three added symbols, no bump
+    driven, scan = (open(os.path.join(CSRC, n)).read() for n in ("osc_driven.hip", "osc_scan.h"))
     assert '#include "osc_scan.h"' in slide and '#include "osc_scan.h"' in driven
     for helper in ("struct cplx", "cplx cmul(", "cplx zpow(", "double from_prev(", "void load_run(", "cplx run_from_zero(",
                    "cplx scan_lanes(", "cplx lane_entry(", "cplx tile_exit(", "void join_waves(", "double frame_scan(",
                    "struct frame_pos"):
         assert helper in scan and helper not in driven and helper not in slide, helper
-    sources = [n for n in sorted(os.listdir(csrc)) if n.endswith((".hip", ".h", ".inc", ".cpp"))]
-    assert [n for n in sources if "bool aligned(" in open(os.path.join(csrc, n)).read()] == ["ds_common.h"]  # ds::aligned
+    sources = [n for n in sorted(os.listdir(CSRC)) if n.endswith((".hip", ".h", ".inc", ".cpp"))]
+    assert [n for n in sources if "bool aligned(" in open(os.path.join(CSRC, n)).read()] == ["ds_common.h"]  # ds::aligned
     assert "atomic" not in slide.replace("No atomics", "").replace("no atomics", "")
 
 
@@ -63,18 +50,14 @@ BAD_BWD = [(dict(gy=None), "null pointer"), (dict(gd=None), "null pointer"), (di
            (dict(gd=OK + 4), "gd or gw not 8-byte aligned"), (dict(gw=OK + 4), "gd or gw not 8-byte aligned"),
            (dict(gy=OK + 2), "misaligned operand"), (dict(gamp=OK + 2), "misaligned operand"),
            (dict(gforce=OK + 2), "misaligned operand"), (dict(ggain=OK + 2), "misaligned operand")]
-CALLS = [("ds_osc_slide_fwd", FWD, c, t) for c, t in BAD + BAD_FWD] + [("ds_osc_slide_bwd", BWD, c, t) for c, t in BAD + BAD_BWD]
+CALLS, IDS = refusal_calls(("ds_osc_slide_fwd", FWD), ("ds_osc_slide_bwd", BWD), BAD, BAD_FWD, BAD_BWD, id_from=7)
 
 
-@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=[f"{f[7:]}-{next(iter(c))}={next(iter(c.values()))}" for f, _, c, _ in CALLS])
+@pytest.mark.parametrize("fn,order,change,text", CALLS, ids=IDS)
 def test_osc_slide_arguments_are_checked_first(fn, order, change, text):
     """Every host-side refusal: a non-zero status and a message that names the entry point and the reason, in front of any
-    launch (the pointers are fakes that a launch would fault on; the call needs no device)."""
-    lib = _hip_built().lib()
-    args = [dict(GOOD, **change)[k] for k in order]
-    assert getattr(lib, fn)(*args, None) != 0
-    msg = lib.ds_last_error().decode()
-    assert fn in msg and text in msg, msg
+    launch."""
+    assert_refused(fn, order, GOOD, change, text)
 
 
 def test_osc_slide_workspace_query_needs_no_device():

@@ -423,3 +423,17 @@ def test_fused_front_end_does_not_synchronise(shim):
     finally:
         torch.cuda.set_sync_debug_mode("default")
     assert torch.isfinite(f.grad).all() and float(f.grad.abs().max()) > 0 and lin_t.shape == lin.shape
+
+
+def test_clouds_are_formed_on_the_operands_device():
+    """The smallest call - one bin, one frame, one mode - forward and backward, with the operands off the current device."""
+    from _guarded import same_on_other_device
+    from diffsound_amd.ddsp.spec_points import spectral_points
+
+    def run(device):
+        P = torch.tensor([[[0.25]]], device=device)
+        freq = torch.tensor([0.5], device=device, requires_grad=True)
+        lin, log = spectral_points(P, freq, 2)
+        return lin.detach(), log.detach(), torch.autograd.grad(lin[..., 3].sum() + 2 * log[..., 3].sum(), freq)[0]
+
+    same_on_other_device(run)
