@@ -189,6 +189,10 @@ _SIGNATURES = {
     "ds_fir_workspace_bytes": (_I64, [_I, _I, _I, _I]),
     "ds_fir_fwd": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "ds_fir_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _I64, _P, _P, _P]),
+    # late reverberation: fdn.hip
+    "ds_fdn_workspace_bytes": (_I64, [_I, _I, _I, _I]),
+    "ds_fdn_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+    "ds_fdn_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
     # Hertz hammer coupled to the modes: contact.hip
     "ds_contact_workspace_bytes": (_I64, [_I, _I, _I, _I]),
     "ds_contact_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _D, _P, _P]),

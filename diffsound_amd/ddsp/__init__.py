@@ -1,3 +1,4 @@
 from .biquad import ParametricEQ, biquad_cascade, highpass_biquad, lowpass_biquad  # noqa: F401
 from .reverb import RoomResponse, fir_convolve  # noqa: F401
+from .fdn import FeedbackDelayNetwork, fdn_reverb  # noqa: F401
 from .contact import HertzHammer, contact_force  # noqa: F401

@@ -855,6 +855,54 @@ int ds_fir_fwd(const float* x, const double* h, int B, int H, int N, int L, floa
 int ds_fir_bwd(const float* gy, const float* x, const double* h, int B, int H, int N, int L, void* work, int64_t work_bytes,
                float* gx /*or NULL*/, double* gh /*or NULL*/, ds_stream_t stream);
 
+/* Late reverberation (still ABI 45, three added symbols): a feedback delay network (FDN) over B rows of N samples - the
+ * late field of a room in a few dozen coefficients where ds_fir_* spends one per tap, at a cost per sample that does not
+ * depend on the tail's length.  n delay lines, H coefficient sets; B is a multiple of H and row b uses set b mod H, as in
+ * ds_fir_*.  Everything starts from rest, s[t < 0] = 0:
+ *   q_j[t] = (1 - p_j) s_j[t - m_j] + p_j s_j[t - m_j - 1]      line j's output: its delay and a two-tap absorption low-pass ;
+ *   s_i[t] = b_i x[t] + sum_j A_ij q_j[t]                       what enters line i ;
+ *   y[t]   = d x[t]   + sum_j c_j q_j[t].
+ * Backward, r the gradient at q and l the gradient at s, both 0 from N on:
+ *   l_i[t] = (1 - p_i) r_i[t + m_i] + p_i r_i[t + m_i + 1] ;   r_j[t] = c_j gy[t] + sum_i A_ij l_i[t] ;
+ *   gx[t] = d gy[t] + sum_i b_i l_i[t] ;   gb_i = sum_t l_i[t] x[t] ;   gA_ij = sum_t l_i[t] q_j[t] ;   gc_j = sum_t gy[t] q_j[t] ;
+ *   gd = sum_t gy[t] x[t] ;   gp_j = sum_t r_j[t] (s_j[t-m_j-1] - s_j[t-m_j]) ;   the parameter sums also run over the rows b = r, r + H, ...
+ *   of a set.
+ * x, y, gy, gx: (B x N) f32, 4-byte aligned.  delays: (H x n) int32, DEVICE memory, every one at least DS_FDN_MIN_DELAY (a delay
+ * may exceed N: a line that never returns).  A, gA: (H x n x n) f64, row i what enters line i; b, c, p, gb, gc, gp: (H x n) f64;
+ * d, gd: (H) f64; p NULL = 0 (the same bits as an array of zeros), else 0 <= p_j <= 0.5 for a low-pass; 8-byte aligned.  state:
+ * (B x n x N) f64, s, written by the forward and read by the backward.  1 <= H <= B <= DS_FDN_MAX_ROWS, 1 <= n <= DS_FDN_MAX_LINES.
+ * All arithmetic in fp64; y and gx are rounded to fp32 once, on the store.  Sums over j start from the x (gy) term and add j
+ * ascending.  BIT FOR BIT, for finite inputs: c = 0, d = 1 returns x (a negative zero is the number zero and comes out as +0);
+ * A = 0, b_j = c_j = 1, d = 0, p = 0 returns the sum over j of x shifted by m_j, with exact zeros in front.
+ * One workgroup a row walks the row in blocks of T = min(min_j m_j, 256) samples, one lane a sample, the n x n product in
+ * registers against the set's coefficients in LDS: every delay reaches back at least T, so a block reads only state that
+ * earlier blocks wrote, and the workgroup barrier between two blocks is the whole hand-off.  The backward is the same loop
+ * in reverse time with A transposed; its history r takes the first 8 B n N bytes of the workspace.  The parameter sums are
+ * split into chunks of 1024 samples (a constant, never a function of the device), the chunks' partial sums go to the
+ * workspace and a second launch adds them, chunks ascending and then rows ascending:
+ * ds_fdn_workspace_bytes(B, H, N, n) = 8 B (n N + ceil(N / 1024) (n^2 + 3 n + 1)) bytes (0 for arguments that would be refused),
+ * 16-byte aligned.  No atomics, no read-modify-write in memory, no workgroup waits for another: the same inputs give the
+ * same bits on any device.  gx, gA, gb, gc, gd, gp may each be NULL: what is NULL is not computed and does not change the
+ * bits of the rest.  Asynchronous on the stream, no allocation.
+ * SAFE FOR EVERY x, gy AND COEFFICIENT: no index and no trip count depends on them.  Non-finite inputs and unstable A yield
+ * inf or NaN in the outputs of their rows and nothing else.  THE DELAYS ARE NEVER READ ON THE HOST: a delay below
+ * DS_FDN_MIN_DELAY is the caller's to refuse (diffsound_amd.ddsp.fdn does); the kernels read such a delay as DS_FDN_MIN_DELAY, so no
+ * index leaves the row whatever the array holds.
+ * Refused (DS_ERR_ARG, message in ds_last_error()), before any device work, in this order: a null required pointer (every
+ * pointer but p and the backward's six outputs); B, H, N or n <= 0; B above DS_FDN_MAX_ROWS; n above DS_FDN_MAX_LINES; H > B or B
+ * not a multiple of H; a misaligned operand; (backward) every output NULL; a misaligned workspace; work_bytes below the
+ * query. */
+#define DS_FDN_MAX_LINES 16   /* n: a lane holds the n line outputs of its sample in registers */
+#define DS_FDN_MIN_DELAY 64   /* m_j: a block of the recursion is at least one wavefront */
+#define DS_FDN_MAX_ROWS 65535 /* B */
+int64_t ds_fdn_workspace_bytes(int B, int H, int N, int n);
+int ds_fdn_fwd(const float* x, const int32_t* delays, const double* A, const double* b, const double* c, const double* d,
+               const double* p /*or NULL*/, int B, int H, int N, int n, double* state, float* y, ds_stream_t stream);
+int ds_fdn_bwd(const float* gy, const float* x, const int32_t* delays, const double* A, const double* b, const double* c,
+               const double* d, const double* p /*or NULL*/, int B, int H, int N, int n, const double* state, void* work,
+               int64_t work_bytes, float* gx /*or NULL*/, double* gA /*or NULL*/, double* gb /*or NULL*/, double* gc /*or NULL*/,
+               double* gd /*or NULL*/, double* gp /*or NULL*/, ds_stream_t stream);
+
 /* Contact force (still ABI 45, three added symbols): a Hertz hammer - mass[a] > 0, approach speed vel[a], contact stiffness
  * stiff[a] > 0, exponent p >= 1 (1.5 for Hertz) - coupled to the m modes (d [1/s], w [rad/s, damped]: the banks' pair) of the
  * object it strikes through the modal gains gain[a,i] at the contact point (ds_mode_sample_fwd).  The reference has no
