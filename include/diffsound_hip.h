@@ -933,6 +933,41 @@ int ds_contact_bwd(const float* gforce, const double* d, const double* w, const 
                    int64_t work_bytes, double* gd /*or NULL*/, double* gw /*or NULL*/, double* ggain /*or NULL*/,
                    double* gmass /*or NULL*/, double* gvel /*or NULL*/, double* gstiff /*or NULL*/, ds_stream_t stream);
 
+/* Friction excitation (still ABI 45, three added symbols): a bow, a rubbing finger or a wet rim - velocity vb[a,k] and normal
+ * force N[a,k] >= 0 per clip and output sample (A x F, the gesture), the friction curve's peak velocity vs[a] > 0 - coupled to the
+ * m modes (d > 0 [1/s], w > 0 [rad/s, damped]: the banks' pair) of the object it rubs through the modal gains gain[a,i] at the
+ * contact point (ds_mode_sample_fwd).  The force is no input: it follows from the object's own velocity under the bow.  The
+ * reference has no counterpart.  With h = 1 / (sr R), z_i = exp((-d_i + i w_i) h), g_i = gain[a,i]^2, r_i = d_i / w_i, and s_i = 0
+ * at n = 0, for n = 0 .. F R - 1 and k = n / R:
+ *   v = sum_i g_i (Re s_i - r_i Im s_i) ;  vr = vb[a,k] - v ;  phi = (vr / vs) exp((1 - (vr / vs)^2) / 2) ;  f = N[a,k] phi ;
+ *   force[a,k] += f / R ;  s_i = z_i (s_i + h f).
+ * phi is odd, peaks at 1 where vr = vs and falls beyond: the steep branch around 0 is sticking, the falling one sustains the
+ * oscillation.  fp64 throughout, force (A x F) stored as f32 (one rounding, after the sample's R contributions are summed in
+ * ascending n), as the banks take it.  N = 0 for a whole clip: the clip's force and all its gradients but gN are exact zeros.
+ * Explicit: stable while h max(N) (sqrt(e) / vs) sum_i g_i << 2, R is the remedy; a non-finite result is not detected.
+ * ds_friction_bwd is the exact adjoint of that recursion: from gforce (A x F) f32, gd, gw (m) summed over the clips in ascending
+ * order, ggain (A x m), gvb, gN (A x F), gvs (A), all f64.  The groups gd with gw; ggain; gvb with gN; gvs may each be NULL: what
+ * is NULL is neither accumulated nor written, and the rest keeps its bits.  CHECKPOINTED: it runs the forward again and keeps
+ * s_i only where a sample begins, then re-runs each sample's R substeps from its checkpoint into one segment per clip before
+ * it walks them backwards - the same instructions in the same order as the forward, so the adjoint is exact for the forward
+ * that ran.  work: ds_friction_workspace_bytes(A, m, F, R) = 16 (A F m + A R m + A m) bytes (checkpoints, segments, the per-clip
+ * (gd, gw) partials; 0 for arguments that would be refused), 16-byte aligned.  One wavefront per clip, no atomics, the same bits
+ * from the same inputs in every output and in the workspace; asynchronous on the stream, no allocation, no synchronisation.
+ * Refused (DS_ERR_ARG, message in ds_last_error()), in this order: a null required pointer; A outside
+ * 1..DS_FRICTION_MAX_CLIPS; m outside 1..DS_FRICTION_MAX_MODES; R outside 1..DS_FRICTION_MAX_OVERSAMPLE; F < 1; F R above
+ * DS_FRICTION_MAX_SUBSTEPS; sr <= 0; half a gradient pair; work_bytes below the query; a misaligned workspace or operand. */
+#define DS_FRICTION_MAX_MODES 512         /* 8 modes per wavefront lane, in registers */
+#define DS_FRICTION_MAX_OVERSAMPLE 64     /* R: a lane per substep of a sample holds its vr */
+#define DS_FRICTION_MAX_CLIPS 65535       /* A */
+#define DS_FRICTION_MAX_SUBSTEPS 16777216 /* F R */
+int64_t ds_friction_workspace_bytes(int A, int m, int F, int R);
+int ds_friction_fwd(const double* d, const double* w, const double* gain, const double* vb, const double* N, const double* vs,
+                    int A, int m, int F, int R, double sr, float* force, ds_stream_t stream);
+int ds_friction_bwd(const float* gforce, const double* d, const double* w, const double* gain, const double* vb, const double* N,
+                    const double* vs, int A, int m, int F, int R, double sr, void* work, int64_t work_bytes,
+                    double* gd /*or NULL*/, double* gw /*or NULL*/, double* ggain /*or NULL*/, double* gvb /*or NULL*/,
+                    double* gN /*or NULL*/, double* gvs /*or NULL*/, ds_stream_t stream);
+
 /* Filtered-noise branch (ABI 44; reference src/ddsp/filtered_noise.py:20-67, FilteredNoise.forward and its autograd): per
  * frame of F samples, L logits -> magnitudes -> a Hann-windowed linear-phase FIR of T = 2 L - 1 taps, applied to a white-noise
  * frame and overlap-added at stride F.  nf = S / F + 1 frames.
