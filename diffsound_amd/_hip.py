@@ -201,6 +201,10 @@ _SIGNATURES = {
     "ds_friction_workspace_bytes": (_I64, [_I, _I, _I, _I]),
     "ds_friction_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),
     "ds_friction_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P, _P]),
+    # tension-modulated modal bank: nlbank.hip
+    "ds_nlbank_workspace_bytes": (_I64, [_I, _I, _I, _I, _I]),
+    "ds_nlbank_fwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _P]),
+    "ds_nlbank_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _D, _P, _I64, _P, _P, _P, _P, _P, _P, _P, _P]),
     # filtered noise: filtered_noise.hip
     "ds_filtered_noise_fwd": (_I, [_P, _P, _I, _I, _I, _I, _D, _P, _P]),
     "ds_filtered_noise_bwd": (_I, [_P, _P, _P, _I, _I, _I, _I, _D, _P, _P]),

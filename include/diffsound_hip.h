@@ -968,6 +968,46 @@ int ds_friction_bwd(const float* gforce, const double* d, const double* w, const
                     double* gd /*or NULL*/, double* gw /*or NULL*/, double* ggain /*or NULL*/, double* gvb /*or NULL*/,
                     double* gN /*or NULL*/, double* gvs /*or NULL*/, ds_stream_t stream);
 
+/* Tension-modulated modal bank (still ABI 45, three added symbols): the m modes (d [1/s], w > 0 [rad/s, damped]: the banks' pair)
+ * of a thin object struck hard, stiffened by the stretching of its own mid-surface - the quartic energy
+ * V = 1/4 sum_r gamma_r (sum_i C_ri q_i^2)^2 of Kirchhoff-Carrier (strings) and Berger (plates) on top of the modal quadratic
+ * one.  The nonlinearity sits inside the bank: the input is a force f (A x F) f64, the output the sound y (A x S) f32.  gain
+ * (A x m): the mode shapes at the contact, amp (A x m): the output gains, C (K x m) >= 0: the stretch coefficients, shared by the
+ * clips, gamma (A x K) >= 0: the coupling strengths.  The reference has no counterpart.  With h = 1 / (sr R),
+ * z_i = exp((-d_i + i w_i) h) and s_i = 0 at n = 0, for n = 0 .. S R - 1 and k = n / R:
+ *   q_i = Im s_i / w_i ;  E_r = sum_i C[r,i] q_i^2 ;  T_r = gamma[a,r] E_r ;  kap_i = sum_r C[r,i] T_r ;
+ *   p_i = gain[a,i] f[a,k] - kap_i q_i  (f[a,k] = 0 for k >= F) ;  s_i = z_i (s_i + h p_i) ;
+ *   if n = k R + R - 1:  y[a,k] = sr sum_i amp[a,i] Im s_i.
+ * fp64 throughout, y stored as f32 (one rounding).  gamma = 0 and R = 1: y is ds_osc_driven_fwd's with the amplitudes amp gain.
+ * Force samples at k >= S are not read.  A clip whose gamma is 0 throughout takes the same path: its nonlinear terms are exact
+ * zeros.  Explicit: stable while h sqrt(max_i kap_i) << 2 at the largest amplitude reached, R is the remedy; a non-finite result
+ * is not detected.
+ * ds_nlbank_bwd is the exact adjoint of that recursion: from gy (A x S) f32, gd, gw (m) and gC (K x m) summed over the clips in
+ * ascending order, ggain, gamp (A x m), gf (A x F; exact zeros at k >= S), ggamma (A x K), all f64.  The groups gd with gw; ggain;
+ * gamp; gf; gC; ggamma may each be NULL: what is NULL is neither accumulated nor written, and the rest keeps its bits.
+ * CHECKPOINTED like ds_friction_bwd: s_i is kept only where a sample begins, each sample's R substeps are re-run from its
+ * checkpoint into one segment per clip - the same instructions in the same order as the forward - and walked backwards.
+ * work: ds_nlbank_workspace_bytes(A, m, K, S, R) = 16 (A S m + A R m + A m) + 8 A K m bytes (checkpoints, segments, the per-clip
+ * (gd, gw) partials, the per-clip gC partials; 0 for arguments that would be refused), 16-byte aligned.  One wavefront per clip,
+ * no atomics, the same bits from the same inputs in every output and in the workspace; asynchronous on the stream, no
+ * allocation, no synchronisation.
+ * Refused (DS_ERR_ARG, message in ds_last_error()), in this order: a null required pointer; A outside 1..DS_NLBANK_MAX_CLIPS; m
+ * outside 1..DS_NLBANK_MAX_MODES; K outside 1..DS_NLBANK_MAX_TERMS; R outside 1..DS_NLBANK_MAX_OVERSAMPLE; F < 1; S < 1; S R above
+ * DS_NLBANK_MAX_SUBSTEPS; sr <= 0; half of (gd, gw); work_bytes below the query; a misaligned workspace or operand. */
+#define DS_NLBANK_MAX_MODES 512         /* 8 modes per wavefront lane, in registers */
+#define DS_NLBANK_MAX_TERMS 4           /* K: stretch terms, each one wave sum a substep */
+#define DS_NLBANK_MAX_OVERSAMPLE 64     /* R: a lane per substep of a sample holds its E_r */
+#define DS_NLBANK_MAX_CLIPS 65535       /* A */
+#define DS_NLBANK_MAX_SUBSTEPS 16777216 /* S R */
+int64_t ds_nlbank_workspace_bytes(int A, int m, int K, int S, int R);
+int ds_nlbank_fwd(const double* d, const double* w, const double* gain, const double* amp, const double* f, const double* C,
+                  const double* gamma, int A, int m, int K, int F, int S, int R, double sr, float* y, ds_stream_t stream);
+int ds_nlbank_bwd(const float* gy, const double* d, const double* w, const double* gain, const double* amp, const double* f,
+                  const double* C, const double* gamma, int A, int m, int K, int F, int S, int R, double sr, void* work,
+                  int64_t work_bytes, double* gd /*or NULL*/, double* gw /*or NULL*/, double* ggain /*or NULL*/,
+                  double* gamp /*or NULL*/, double* gf /*or NULL*/, double* gC /*or NULL*/, double* ggamma /*or NULL*/,
+                  ds_stream_t stream);
+
 /* Filtered-noise branch (ABI 44; reference src/ddsp/filtered_noise.py:20-67, FilteredNoise.forward and its autograd): per
  * frame of F samples, L logits -> magnitudes -> a Hann-windowed linear-phase FIR of T = 2 L - 1 taps, applied to a white-noise
  * frame and overlap-added at stride F.  nf = S / F + 1 frames.
